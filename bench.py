@@ -62,12 +62,44 @@ def emit(res):
 
 T_START = time.time()
 
+DUMP_BYTES = 64 << 20               # --dump-outputs: at most this much in all
+DUMP_SAMPLE_ELEMS = 4 << 20         # a trainer-state array larger than this is written as a fixed, seeded sample
+
+
+def dump_outputs(path, out, state):
+    """--dump-outputs: what the timed path computed in its last step, as <path>/<name>.npy (float32, or float64 for
+    integers and fp64 tensors).  `out` is train_step's return value, written whole; `state` holds the trainer arrays the
+    step updated (parameters, MoCo queue), each reduced to a sample at indices drawn from a fixed seed when it is large."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in sorted(out.items()):
+        arrays[name] = t.detach()
+    for name, t in state.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE_ELEMS]
+            t, name = t.reshape(-1)[idx.sort().values.to(t.device)], name + '_sample'
+        arrays[name] = t
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        a = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.dtype != np.float64 else np.float64)
+        total += a.nbytes
+        if total > DUMP_BYTES:
+            raise RuntimeError('--dump-outputs: more than %d MB' % (DUMP_BYTES >> 20))
+        np.save(os.path.join(path, name + '.npy'), a)
+    log('dumped %d arrays (%.1f MB) to %s' % (len(arrays), total / 1e6, path))
+
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--steps', type=int, default=50, help='timed steps (at least 1)')
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help="after the timed steps, write the arrays the last timed step returned (and a fixed, seeded sample "
+                         "of the parameters and queue it updated) to DIR/<name>.npy; rank 0's, when N > 1")
     ap.add_argument('--batch', type=int, default=0, help='clips per GPU (default 32; 16 with --math fp16)')
     ap.add_argument('--frames', type=int, default=0, help='default 16 (32 with --math fp16)')
     ap.add_argument('--size', type=int, default=0, help='default 112 (224 with --math fp16)')
@@ -91,6 +123,8 @@ def parse():
                     help="moco: BASELINE configs[1]/[2] (default, the headline line); simsiam: configs[3] -- "
                          "configs/visual_simsiam.yaml shape: S3D, 16x224x224, FEAT_DIM 1024, temporal-graph blocks on, 4 clips/GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     base = FP16_DEFAULTS if args.math == 'fp16' else dict(backbone='R2P1D18', frames=16, size=112, batch=32)
     if args.workload == 'simsiam':
         base = dict(backbone='S3D', frames=16, size=224, batch=4)
@@ -409,6 +443,8 @@ def simsiam_main(args, pkg, dev, ctx, world, rank, barrier):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     loss = float(out['loss'].item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, {'params': tr.arena.flat})
     tr.close()
     del tr
     if rank != 0:
@@ -478,6 +514,7 @@ def simsiam_subrecord(pkg, dev, ctx, args):
     import gc
     a = argparse.Namespace(**vars(args))
     a.workload, a.backbone, a.frames, a.size, a.batch = 'simsiam', 'S3D', 16, 224, 4
+    a.dump_outputs = ''                  # the dump is the headline path's
     rec = simsiam_main(a, pkg, dev, ctx, 1, 0, torch.cuda.synchronize)
     gc.collect()
     torch.cuda.empty_cache()
@@ -684,6 +721,8 @@ def main():
     if rank != 0:
         return
     log('timed region %.3fs, loss %.4f' % (dt, loss))
+    if args.dump_outputs:            # before anything else runs on this trainer (the input-stage sub-record does)
+        dump_outputs(args.dump_outputs, out, {'params': tr.arena_q.flat, 'queue': tr.contrast.memory})
     global_batch = args.batch * world
     value = global_batch * args.steps / dt
     step_gflop = 4 * FWD_GFLOP_PER_VIEW * args.batch if (args.backbone, args.frames, args.size) == ('R2P1D18', 16, 112) else None
