@@ -80,11 +80,11 @@ def test_conv_f16_storage_vs_f32_of_rounded_operands(ops, shape, K, k, s, p):
     assert dw.dtype is torch.float32
     assert rel_err(dw, wr.grad) < TOL_F
     if k == (1, 1, 1) and s == (1, 1, 1) and (shape[2] * shape[3] * shape[4]) % 8 == 0 and shape[2] * shape[3] * shape[4] >= 128:
-        assert (plan.cfg(0)[3] >> 17) & 1 and (plan.cfg(1)[3] >> 17) & 1              # the pointwise GEMM kernel ran both passes
+        assert plan.kernel(0) == 'pw' and plan.kernel(1) == 'pw'              # the pointwise GEMM kernel ran both passes
         for name in ('fwd', 'dgrad'):                                                 # ... and agrees with the gather kernels
             setattr(plan.g, 'tune_%s_bm' % name, 64)
         plan.refresh()
-        assert not (plan.cfg(0)[3] >> 17) & 1
+        assert plan.kernel(0) != 'pw'
         y2, (ss2, sq2) = ops.conv_fwd(plan, xd, ops.conv_pack(plan, 0, wd), None, stats=True)
         dx2 = ops.conv_dgrad(plan, dyd, ops.conv_pack(plan, 1, wd))
         assert rel_err(y.float(), y2.float()) < TOL_H and rel_err(dx.float(), dx2.float()) < TOL_H
@@ -113,7 +113,7 @@ def test_conv_f16_every_halo_box_and_gather_tile(ops):
             setattr(plan.g, 'tune_%s_bm' % name, code)
             setattr(plan.g, 'tune_%s_box' % name, box)
             plan.refresh()
-            seen.add((which, (plan.cfg(which)[3] >> 14) & 1))
+            seen.add((which, plan.kernel(which) == 'halo'))
             if which == 0:
                 out = ops.conv_fwd(plan, x, ops.conv_pack(plan, 0, w), None).float()
                 assert rel_err(out, yr) < TOL_H

@@ -201,14 +201,14 @@ def test_conv_halo_kernels_every_configuration(ops, ctol, shape, K, k, s, p):
                     plan.g.tune_fwd_box = plan.g.tune_dgrad_box = code
                     plan.g.tune_fwd_splits = plan.g.tune_dgrad_splits = sp
                     plan.refresh()
-                    if (plan.cfg(0)[3] >> 14) & 1:
+                    if plan.kernel(0) == 'halo':
                         assert plan.cfg(0)[:2] == (rows, bn)
                         y, (ss, sq) = ops.conv_fwd(plan, xd, ops.conv_pack(plan, 0, wd), None, stats=True)
                         assert rel_err(y, yr) < ctol, ('fwd', rows, box, sp)
                         assert rel_err(ss.sum(1), yr.detach().sum((0, 2, 3, 4))) < 1e-4, ('sum', rows, box, sp)
                         assert rel_err(sq.sum(1), (yr.detach() ** 2).sum((0, 2, 3, 4))) < 1e-4, ('sq', rows, box, sp)
                         ran[0] += 1
-                    if (plan.cfg(1)[3] >> 14) & 1:
+                    if plan.kernel(1) == 'halo':
                         dx = ops.conv_dgrad(plan, dyd, ops.conv_pack(plan, 1, wd))
                         assert rel_err(dx, xr.grad) < ctol, ('dgrad', rows, box, sp)
                         acc = torch.ones_like(dx)
@@ -230,7 +230,7 @@ def test_conv_halo_kernels_every_configuration(ops, ctol, shape, K, k, s, p):
         box = _boxes(128, qf, s, k)[0]
         pv.g.tune_fwd_bm, pv.g.tune_fwd_box = 64 | 2048, box[0] | (box[1] << 8) | (box[2] << 16)
         pv.refresh()
-        assert (pv.cfg(0)[3] >> 14) & 1
+        assert pv.kernel(0) == 'halo'
         yv = ops.conv_fwd(pv, xv, ops.conv_pack(pv, 0, wd), bias.to(DEV))
         want = F.conv3d(torch.chunk(both, 2, dim=1)[view], w, bias, s, p)
         assert rel_err(yv, want) < ctol, ('view', view)
@@ -259,12 +259,12 @@ def test_conv_stem_kernel_vs_gather_and_aten(ops, ctol, shape, K, k, s, p, bias)
     outs = {}
     plan.g.tune_fwd_bm = 4096 | 64
     plan.refresh()
-    runnable = (plan.cfg(0)[3] >> 16) & 1          # (the 7x7x7 halo of a 256-position box does not fit LDS in three bf16 parts)
+    runnable = plan.kernel(0) == 'stem'          # (the 7x7x7 halo of a 256-position box does not fit LDS in three bf16 parts)
     assert runnable == (0 if ops.get_conv_math() == 'f32' or (k == (7, 7, 7) and ops.get_conv_math() == 'bf16x6') else 1)
     for name, code in (('default', 0), ('stem', 4096 | 64), ('gather', 64)):
         plan.g.tune_fwd_bm = code
         plan.refresh()
-        stem = (plan.cfg(0)[3] >> 16) & 1
+        stem = plan.kernel(0) == 'stem'
         assert stem == (0 if name == 'gather' else runnable), (name, stem)      # the un-tuned default takes it whenever it can run
         y, (ss, sq) = ops.conv_fwd(plan, xd, ops.conv_pack(plan, 0, wd), bd, stats=True)
         assert ss.shape[1] == plan.parts
@@ -1130,7 +1130,7 @@ def test_conv_consumes_producer_batchnorm_relu_on_the_fly(ops, shape, K, kd, pd)
             plan.g.tune_fwd_bm, plan.g.tune_fwd_box = 64 | 2048, box[0] | (box[1] << 8) | (box[2] << 16)
             plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = 11, 2
             plan.refresh()
-            assert (plan.cfg(0)[3] >> 14) & 1 and plan.cfg(2)[3] & 255 == 11
+            assert plan.kernel(0) == 'halo' and plan.cfg(2)[3] & 255 == 11
             assert ops.conv_xf_ok(plan)
             wp = ops.conv_pack(plan, 0, w)
             o1, (s1, q1) = ops.conv_fwd(plan, z, wp, None, stats=True)

@@ -352,6 +352,82 @@ def test_exchange_plan_bookkeeping(pkg):
             assert send_counts[d] == sends[d][2][r]          # what r sends to d is what d expects from r
 
 
+# Inputs of a conv launch-plan record: every gca_conv_geom field, the arithmetic mode in force, the pass (0 fwd, 1 dgrad).
+CONV_GEOM_FIELDS = ('N', 'C', 'D', 'H', 'W', 'K', 'kd', 'kh', 'kw', 'sd', 'sh', 'sw', 'pd', 'ph', 'pw', 'OD', 'OH', 'OW',
+                    'x_batch_stride', 'tune_fwd_bm', 'tune_fwd_splits', 'tune_dgrad_bm', 'tune_dgrad_splits',
+                    'tune_wgrad_splits', 'tune_wgrad_tile', 'tune_fwd_tail', 'tune_dgrad_tail', 'tune_fwd_math',
+                    'tune_dgrad_math', 'tune_wgrad_math', 'tune_fwd_box', 'tune_dgrad_box', 'act_f16')
+
+
+def conv_launch_record(H, row):
+    """Everything the host side derives for one (geometry, tune codes, arithmetic mode, pass): kernel configuration word,
+    BatchNorm partial count, work-space bytes, packed-weight size and layout, gather-table rows, whether the fused-input
+    forward applies, and digests of the gather table and of the weight re-layout job records (fixed dummy pointers)."""
+    import ctypes as C
+    import hashlib
+    g = H.ConvGeom(*[int(v) for v in row[:len(CONV_GEOM_FIELDS)]])
+    math, which = int(row[-2]), int(row[-1])
+    assert H.lib.gca_set_conv_math(math) == 0
+    gp = C.byref(g)
+    digest = lambda b: int.from_bytes(hashlib.sha256(b).digest()[:8], 'little', signed=True)
+    cfg = (C.c_int32 * 4)()
+    out = [H.lib.gca_conv_kernel_cfg(gp, which, cfg)] + list(cfg)
+    out += [H.lib.gca_conv_fwd_stat_parts(gp), H.lib.gca_conv_xf_ok(gp),
+            (H.lib.gca_conv_fwd_ws_bytes if which == 0 else H.lib.gca_conv_dgrad_ws_bytes)(gp),
+            H.lib.gca_conv_pack_elems(gp, which), H.lib.gca_conv_pack_layout(gp, which)]
+    rows = H.lib.gca_conv_table_rows(gp, which)
+    tab = (C.c_int32 * (2 * max(rows, 0)))()
+    out += [rows, H.lib.gca_conv_table_build_host(gp, which, tab), digest(bytes(tab))]
+    njobs = H.lib.gca_conv_pack_jobs_host(gp, which, None, None, None)
+    jobs = (C.c_ubyte * (H.PACK_JOB_BYTES * max(njobs, 0)))()
+    out += [njobs, H.lib.gca_conv_pack_jobs_host(gp, which, 1 << 20, 1 << 32, jobs), digest(bytes(jobs))]
+    return out
+
+
+def test_conv_launch_plans_match_the_golden_dump(pkg):
+    """Host logic only, no launch: for every geometry of profiles/tune_cache.json (its pinned tune codes and the all-zero
+    heuristic, arithmetic modes 0 / 1 / 2, fp16 storage where it was tuned) and both passes, the launch plan the library
+    derives -- kernel, tile, splits, work-space, packed layout, gather table, pack jobs -- is the recorded one."""
+    for knob in ('GCA_HALO', 'GCA_PW', 'GCA_STEM'):
+        if os.environ.get(knob):
+            pytest.skip('%s changes the heuristic launch choice' % knob)
+    z = np.load(os.path.join(ROOT, 'tests', 'golden', 'conv_launch.npz'))
+    H = pkg._hip
+    default = H.lib.gca_get_conv_math()
+    try:
+        for row, want in zip(z['inputs'], z['outputs']):
+            got = conv_launch_record(H, row)
+            assert got == want.tolist(), dict(zip(CONV_GEOM_FIELDS + ('math', 'which'), row.tolist()))
+    finally:
+        H.lib.gca_set_conv_math(default)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='dummy operand pointers: only meaningful where nothing can run')
+def test_conv_fwd_slabs_refuses_non_split_launches_before_launching(pkg):
+    """gca_conv_fwd_slabs leaves split-K slabs, so a pass whose resolved launch does not split (or runs a kernel without
+    slabs: stem, pointwise fp16) is refused with GCA_EINVAL before anything is launched.  The operands are dummy pointers on
+    a null stream: a launch attempt here would report GCA_ELAUNCH (-2), not -1."""
+    H = pkg._hip
+    import ctypes as C
+    ops = pkg.engine.ops
+    cpu = torch.device('cpu')
+    default = H.lib.gca_get_conv_math()
+    try:
+        H.lib.gca_set_conv_math(2)                                              # bf16x6: the stem kernel can run
+        cases = ((ops.ConvPlan(2, 16, 4, 8, 8, 40, 3, 1, 1, cpu), 64, 1, 'gather'),
+                 (ops.ConvPlan(4, 3, 8, 56, 56, 45, (1, 7, 7), (1, 2, 2), (0, 3, 3), cpu), ops.TUNE_STEM | 64, 0, 'stem'),
+                 (ops.ConvPlan(2, 256, 2, 8, 8, 128, 1, 1, 0, cpu, act_f16=True), ops.TUNE_PW | 128, 0, 'pw'))
+        for plan, code, sp, kernel in cases:
+            plan.g.tune_fwd_bm, plan.g.tune_fwd_splits = code, sp
+            assert plan.kernel(0) == kernel and plan.cfg(0)[2] == 1
+            splits = C.c_int32(-7)
+            dummy = 1 << 20
+            assert H.lib.gca_conv_fwd_slabs(plan.gp, dummy, dummy, dummy, dummy, C.addressof(splits), None) == -1, kernel
+            assert splits.value == -7
+    finally:
+        H.lib.gca_set_conv_math(default)
+
+
 def test_bench_stdout_carries_only_the_result_line():
     """bench.py's contract is ONE JSON line on stdout.  RCCL writes a version banner to file descriptor 1 from native code when
     the first communicator is created (seen on the GPU box), so bench.py points descriptor 1 at stderr and emits the result

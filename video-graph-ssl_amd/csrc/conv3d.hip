@@ -713,10 +713,6 @@ __global__ __launch_bounds__(256) void conv_igemm_2phase_kernel(
 
 // Split-K finishing pass, grid (channels, parts): sum the slabs in fixed order, add bias, (+=) store in
 // NCDHW (through the class's destination map), and emit the BN partial sums [K][parts].
-// gca_conv_fwd_slabs: the split-K classes leave their slabs un-finished (the BatchNorm that follows folds them)
-thread_local bool t_leave_slabs = false;
-thread_local int t_left_splits = 0;
-
 constexpr int FINISH_CHUNK = 1024;      // columns per finishing block: split-K grids are small, so many short blocks (4 columns per thread;
                                         // issuing the slab loads of all four columns together was measured: 9.1 vs 8.6 us per launch, not kept)
 template <typename T>
@@ -823,21 +819,42 @@ __global__ void zero_fill_kernel(unsigned* __restrict__ p, long long n32, int ta
 }
 
 // ---- launch configuration ------------------------------------------------------------------
+// kernel family of a class: per-tap gathers (this file), LDS halo tiles (conv3d_halo.hip; kt_per_split then counts 16-channel
+// chunks), the stem kernel (conv3d_stem.hip; forward only) and the pointwise fp16 GEMM (conv3d_pw.hip)
+enum class ConvKernel { Gather = 0, Halo = 1, Stem = 2, Pointwise = 3 };   // (value = PackParams::fmt of its weight layout)
+
 struct IgemmCfg {
   int bm; int bn; int splits; int kt_per_split; int tail_bm; int main_cols; int math;
-  int halo;              // 1: conv3d_halo.hip (LDS halo tiles); kt_per_split then counts 16-channel chunks
-  int bd, bh, bw;        // halo: box of a tile
+  ConvKernel kernel;
+  int bd, bh, bw;        // halo / stem: box of a tile
   int h;                 // fp16 storage (gca_set_conv_math(3)): the gather kernels widen on load / round on store and
                          // multiply in bf16x3 (exact for fp16 operands); the halo kernels multiply on the f16 MFMA (math 3)
 };
 
+
+// Split of a reduction of nk steps over `tiles` output tiles of an M x Ntot problem: forced (> 0), or when the tile grid cannot
+// occupy the CUs and the slabs stay small.  -> splits; `per` = steps per split.
+inline int split_k(long long tiles, int nk, long long M, long long Ntot, int force, int& per) {
+  int s = 1;
+  if (force > 0) s = force;
+  else if (tiles < 2 * NUM_CU && nk >= 8 && M * Ntot <= (1LL << 20)) {
+    long long want = gca_ceil_div(2 * NUM_CU, tiles);
+    if (want > nk / 4) want = nk / 4;
+    if (want > 16) want = 16;
+    if (want > 1) s = (int)want;
+  }
+  if (s > nk) s = nk;
+  if (s < 1) s = 1;
+  per = (int)gca_ceil_div(nk, s);
+  return (int)gca_ceil_div(nk, per);
+}
 
 // Heuristic default (the host side may override it per geometry after measuring: gca_conv_geom.tune_*).
 // Tile = 32*TM rows (TM = 1..5, picked to minimise padded rows) x 128 columns, or x 256 columns with float4
 // gathers for pointwise-in-space classes; the K loop is split when the tile grid cannot occupy the CUs and
 // the partial slabs stay small.  tune code: rows | 1024 for the 256-column variant.
 inline IgemmCfg choose_cfg(int M, long long Ntot, int nk, bool vec_ok, int force_bm, int force_splits) {
-  IgemmCfg best{64, 128, 1, nk, 0, 0, 0, 0, 0, 0, 0, 0};
+  IgemmCfg best{64, 128, 1, nk, 0, 0, 0, ConvKernel::Gather, 0, 0, 0, 0};
   double best_cost = 1e300;
   const bool force_vec = force_bm >= 1024;
   const int force_rows = force_bm & 1023;
@@ -848,18 +865,8 @@ inline IgemmCfg choose_cfg(int M, long long Ntot, int nk, bool vec_ok, int force
       const int bm = 32 * tm, bn = v ? 256 : 128;
       if (force_rows && bm != force_rows) continue;
       const long long tiles = gca_ceil_div(M, bm) * gca_ceil_div(Ntot, bn);
-      int s = 1;
-      if (force_splits > 0) s = force_splits;
-      else if (tiles < 2 * NUM_CU && nk >= 8 && (long long)M * Ntot <= (1LL << 20)) {
-        long long want = gca_ceil_div(2 * NUM_CU, tiles);
-        if (want > nk / 4) want = nk / 4;
-        if (want > 16) want = 16;
-        if (want > 1) s = (int)want;
-      }
-      if (s > nk) s = nk;
-      if (s < 1) s = 1;
-      const int per = (int)gca_ceil_div(nk, s);
-      s = (int)gca_ceil_div(nk, per);
+      int per;
+      const int s = split_k(tiles, nk, M, Ntot, force_splits, per);
       const double wg_per_cu = (double)(tiles * s) / NUM_CU;
       const double occ = wg_per_cu < 1.0 ? 0.55 : (wg_per_cu < 2.0 ? 0.75 : 1.0);   // latency hiding needs >= 2 WGs / CU
       const double rounds = (double)gca_ceil_div(tiles * s, NUM_CU);
@@ -867,7 +874,7 @@ inline IgemmCfg choose_cfg(int M, long long Ntot, int nk, bool vec_ok, int force
       const double eff = (0.55 + 0.1 * tm) * (v ? 1.15 : 1.0) * occ;
       const double work = (double)bm * bn * per;
       const double cost = rounds * work / eff + (s > 1 ? 0.05 * rounds * work + 8.0 * bm * bn : 0.0);
-      if (cost < best_cost) { best_cost = cost; best = IgemmCfg{bm, bn, s, per, 0, 0, 0, 0, 0, 0, 0, 0}; }
+      if (cost < best_cost) { best_cost = cost; best = IgemmCfg{bm, bn, s, per, 0, 0, 0, ConvKernel::Gather, 0, 0, 0, 0}; }
     }
   }
   return best;
@@ -1037,13 +1044,13 @@ inline IgemmCfg cfg_for(const gca_conv_geom* g, int which, const ClassInfo& c, c
   if (which == 0 && ((fbm & 4096) || (fbm == 0 && stem_heuristic_on()))) {
     StemParams sp;
     if (stem_geometry(g, p, math, sp))
-      return IgemmCfg{32 * sp.wm, 512 / sp.wm, 1, sp.nsteps, 0, 0, math, 2, sp.bd, sp.bh, sp.bw, math == 3};
+      return IgemmCfg{32 * sp.wm, 512 / sp.wm, 1, sp.nsteps, 0, 0, math, ConvKernel::Stem, sp.bd, sp.bh, sp.bw, math == 3};
   }
   if (fbm & 4096) { fbm = 0; fs = 0; tail = 0; }           // not runnable as asked
   // ---- pointwise fp16 GEMM kernel: forced by tune code 8192, or by the heuristic when un-tuned
   if ((fbm & 8192) || (fbm == 0 && pw_heuristic_on())) {
     PwParams pw;
-    if (pw_geometry(g, which, p, pw)) return IgemmCfg{128, 128, 1, pw.Kpad / 32, 0, 0, 3, 3, 0, 0, 0, 1};
+    if (pw_geometry(g, which, p, pw)) return IgemmCfg{128, 128, 1, pw.Kpad / 32, 0, 0, 3, ConvKernel::Pointwise, 0, 0, 0, 1};
   }
   if (fbm & 8192) { fbm = 0; fs = 0; tail = 0; }
   // ---- LDS-halo kernel: forced by the tune code, or by the heuristic for multi-tap classes with enough channels and tiles
@@ -1073,20 +1080,9 @@ inline IgemmCfg cfg_for(const gca_conv_geom* g, int which, const ClassInfo& c, c
       }
       if (rows >= 32 && rows <= 32 * (bn == 256 ? 4 : 5) && rows % 32 == 0 &&
           halo_lds_bytes(rows, math, hp.P) <= (size_t)(160 << 10) - 1024) {
-        IgemmCfg cf{rows, bn, 1, hp.nchunks, 0, 0, math, 1, bd, bh, bw, math == 3};
+        IgemmCfg cf{rows, bn, 1, hp.nchunks, 0, 0, math, ConvKernel::Halo, bd, bh, bw, math == 3};
         const long long tiles = (long long)cdiv(p.DK, rows) * g->N * hp.nbd * hp.nbh * hp.nbw;
-        int sp = 1;
-        if (fs > 0) sp = fs;
-        else if (tiles < 2 * NUM_CU && hp.nchunks >= 8 && (long long)p.DK * p.Ntot <= (1LL << 20)) {
-          long long want = gca_ceil_div(2 * NUM_CU, tiles);
-          if (want > hp.nchunks / 4) want = hp.nchunks / 4;
-          if (want > 16) want = 16;
-          if (want > 1) sp = (int)want;
-        }
-        if (sp > hp.nchunks) sp = hp.nchunks;
-        if (sp < 1) sp = 1;
-        cf.kt_per_split = cdiv(hp.nchunks, sp);
-        cf.splits = cdiv(hp.nchunks, cf.kt_per_split);
+        cf.splits = split_k(tiles, hp.nchunks, p.DK, p.Ntot, fs, cf.kt_per_split);
         return cf;
       }
     }
@@ -1141,8 +1137,20 @@ void launch_tm(const IgemmCfg& c, int fast, dim3 grid, hipStream_t st, const flo
 
 inline int stat_parts(const IgemmCfg& c, long long Ntot, long long halo_tiles = 0) {
   if (c.splits > 1) return (int)gca_ceil_div(Ntot, FINISH_CHUNK);
-  if (c.halo) return (int)halo_tiles;
+  if (c.kernel != ConvKernel::Gather) return (int)halo_tiles;     // halo / stem kernels: one partial per box tile
   return (int)gca_ceil_div(Ntot, c.bn);
+}
+
+// the split-K finishing pass of a class (p.P parts)
+int finish_slabs(const IgemmCfg& c, const float* slab, const float* bias, float* dst, float* psum, float* psq, const IgemmParams& p,
+                 hipStream_t st) {
+  const dim3 grid((unsigned)p.DK, (unsigned)p.P);
+  if (c.h)
+    hipLaunchKernelGGL(conv_splitk_finish_kernel<_Float16>, grid, dim3(256), 0, st, slab, c.splits, bias,
+                       reinterpret_cast<_Float16*>(dst), psum, psq, p);
+  else
+    hipLaunchKernelGGL(conv_splitk_finish_kernel<float>, grid, dim3(256), 0, st, slab, c.splits, bias, dst, psum, psq, p);
+  return gca_launch_status();
 }
 
 int launch_tiles(int bm, const IgemmCfg& c, int fast, dim3 grid, hipStream_t st, const float* src, const float* apack,
@@ -1157,8 +1165,9 @@ int launch_tiles(int bm, const IgemmCfg& c, int fast, dim3 grid, hipStream_t st,
   return gca_launch_status();
 }
 
+// leave_slabs: a split-K launch stops before its finishing pass (gca_conv_fwd_slabs: the consumer folds the slabs)
 int run_class(const IgemmCfg& c, int fast, const float* src, const float* apack, const int2* table, const float* bias,
-              float* dst, float* psum, float* psq, float* slab, IgemmParams p, hipStream_t st) {
+              float* dst, float* psum, float* psq, float* slab, IgemmParams p, hipStream_t st, bool leave_slabs) {
   const int tilesN = (int)gca_ceil_div(p.Ntot, c.bn);
   p.splits = c.splits; p.kt_per_split = c.kt_per_split;
   p.P = stat_parts(c, p.Ntot);
@@ -1200,21 +1209,14 @@ int run_class(const IgemmCfg& c, int fast, const float* src, const float* apack,
   const long long nblk = (long long)p.tilesM * p.tilesN * c.splits;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return GCA_EINVAL;
   int rc = launch_tiles(c.bm, c, fast, dim3((unsigned)nblk), st, src, apack, table, bias, dst, ps, pq, slab, p);
-  if (rc || c.splits == 1) return rc;
-  if (t_leave_slabs) { t_left_splits = c.splits; return gca_launch_status(); }      // gca_conv_fwd_slabs: the consumer folds them
-  if (c.h)
-    hipLaunchKernelGGL(conv_splitk_finish_kernel<_Float16>, dim3((unsigned)p.DK, (unsigned)p.P), dim3(256), 0, st, slab, c.splits,
-                       bias, reinterpret_cast<_Float16*>(dst), psum, psq, p);
-  else
-    hipLaunchKernelGGL(conv_splitk_finish_kernel<float>, dim3((unsigned)p.DK, (unsigned)p.P), dim3(256), 0, st, slab, c.splits,
-                       bias, dst, psum, psq, p);
-  return gca_launch_status();
+  if (rc || c.splits == 1 || leave_slabs) return rc;
+  return finish_slabs(c, slab, bias, dst, psum, psq, p, st);
 }
 
 // One class on the LDS-halo kernels.  `tapdelta` = the 64-entry tap-delta table that follows the class's gather rows.
 int run_class_halo(const gca_conv_geom* g, const ClassInfo& c, const IgemmCfg& cf, const float* src, const float* apack,
                    const int2* table, const float* bias, float* dst, float* psum, float* psq, float* slab, IgemmParams p,
-                   hipStream_t st, const float* in_scale = nullptr, const float* in_shift = nullptr) {
+                   hipStream_t st, bool leave_slabs, const float* in_scale, const float* in_shift) {
   HaloParams hp;
   if (!halo_geometry(c, p, cf.bd, cf.bh, cf.bw, cf.math, hp)) return GCA_EINVAL;
   hp.in_scale = in_scale; hp.in_shift = in_shift;
@@ -1229,16 +1231,9 @@ int run_class_halo(const gca_conv_geom* g, const ClassInfo& c, const IgemmCfg& c
   HaloCfg hc{cf.bm, cf.bn, cf.bd, cf.bh, cf.bw, cf.splits, cf.kt_per_split, cf.math};
   int rc = halo_launch(hc, hp, src, reinterpret_cast<const unsigned char*>(apack), reinterpret_cast<const int*>(table + p.Kpad),
                        bias, dst, cf.splits > 1 ? nullptr : psum, cf.splits > 1 ? nullptr : psq, slab, st);
-  if (rc || cf.splits == 1) return rc;
-  if (t_leave_slabs) { t_left_splits = cf.splits; return gca_launch_status(); }     // gca_conv_fwd_slabs: the consumer folds them
+  if (rc || cf.splits == 1 || leave_slabs) return rc;
   p.splits = cf.splits; p.P = hp.g.P;
-  if (cf.h)
-    hipLaunchKernelGGL(conv_splitk_finish_kernel<_Float16>, dim3((unsigned)p.DK, (unsigned)p.P), dim3(256), 0, st, slab, cf.splits,
-                       bias, reinterpret_cast<_Float16*>(dst), psum, psq, p);
-  else
-    hipLaunchKernelGGL(conv_splitk_finish_kernel<float>, dim3((unsigned)p.DK, (unsigned)p.P), dim3(256), 0, st, slab, cf.splits,
-                       bias, dst, psum, psq, p);
-  return gca_launch_status();
+  return finish_slabs(cf, slab, bias, dst, psum, psq, p, st);
 }
 
 // A pointwise class on the fp16 GEMM kernel.
@@ -1263,20 +1258,53 @@ int run_class_stem(const gca_conv_geom* g, const IgemmCfg& cf, const float* src,
   return stem_launch(cf.math, sp, src, reinterpret_cast<const unsigned char*>(apack), bias, dst, psum, psq, st);
 }
 
-int64_t ws_bytes_for(const gca_conv_geom* g, int which) {
+// Launch plan of one pass (which: 0 forward, 1 dgrad): its problem classes with their kernel parameters and launch
+// configuration.  The pack layout, the table, the work-space size and the launches are all sized from this one plan.  A class
+// with ntaps == 0 (a dgrad residue no tap reaches) keeps its slot, with zero p / cf: nothing is packed or launched for it.
+struct ConvLaunch {
   std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
-  int64_t need = 0;
-  for (const ClassInfo& c : cls) {
-    if (c.ntaps == 0) continue;
-    IgemmParams p{};
-    class_params(g, which, c, p);
-    const IgemmCfg cf = cfg_for(g, which, c, p, cls.size());
-    if (cf.splits > 1) {
-      const int64_t b = (int64_t)cf.splits * p.DK * p.Ntot * (int64_t)sizeof(float);
-      if (b > need) need = b;
-    }
+  std::vector<IgemmParams> p;
+  std::vector<IgemmCfg> cf;
+};
+
+ConvLaunch resolve_launch(const gca_conv_geom* g, int which) {
+  ConvLaunch L;
+  build_classes(g, which, L.cls);
+  const size_t n = L.cls.size();
+  L.p.assign(n, IgemmParams{});
+  L.cf.assign(n, IgemmCfg{});
+  for (size_t i = 0; i < n; ++i) {
+    if (L.cls[i].ntaps == 0) continue;
+    class_params(g, which, L.cls[i], L.p[i]);
+    L.cf[i] = cfg_for(g, which, L.cls[i], L.p[i], n);
   }
+  return L;
+}
+
+// Class i of a resolved pass on its kernel family.  `apack` / `table` point at the class's own packed weights / gather rows;
+// leave_slabs and in_scale / in_shift (input transform of gca_conv_fwd_xf) apply to the split-K capable / halo kernels only.
+int run_resolved_class(const gca_conv_geom* g, int which, const ConvLaunch& L, size_t i, const float* src, const float* apack,
+                       const int2* table, const float* bias, float* dst, float* psum, float* psq, float* slab, int accumulate,
+                       hipStream_t st, bool leave_slabs = false, const float* in_scale = nullptr, const float* in_shift = nullptr) {
+  const ClassInfo& c = L.cls[i];
+  const IgemmCfg& cf = L.cf[i];
+  IgemmParams p = L.p[i];
+  p.accumulate = accumulate ? 1 : 0;
+  switch (cf.kernel) {
+    case ConvKernel::Pointwise: return run_class_pw(g, which, src, apack, bias, dst, psum, psq, p, st);
+    case ConvKernel::Stem: return run_class_stem(g, cf, src, apack, bias, dst, psum, psq, p, st);
+    case ConvKernel::Halo:
+      return run_class_halo(g, c, cf, src, apack, table, bias, dst, psum, psq, slab, p, st, leave_slabs, in_scale, in_shift);
+    case ConvKernel::Gather: break;
+  }
+  return run_class(cf, fast_of(c.ntaps), src, apack, table, bias, dst, psum, psq, slab, p, st, leave_slabs);
+}
+
+int64_t ws_bytes_for(const gca_conv_geom* g, int which) {
+  const ConvLaunch L = resolve_launch(g, which);
+  int64_t need = 0;
+  for (size_t i = 0; i < L.cls.size(); ++i)
+    if (L.cf[i].splits > 1) need = std::max<int64_t>(need, (int64_t)L.cf[i].splits * L.p[i].DK * L.p[i].Ntot * (int64_t)sizeof(float));
   return need;
 }
 
@@ -1307,21 +1335,15 @@ int gca_get_conv_math(void) { return conv_math(); }
 
 int64_t gca_conv_pack_elems(const gca_conv_geom* g, int which) {
   if (!geom_ok(g) || (which != 0 && which != 1)) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
   int64_t n = 0;
-  for (const ClassInfo& c : cls) n += pack_reserve(c);
+  for (const ClassInfo& c : resolve_launch(g, which).cls) n += pack_reserve(c);
   return n > 0 ? n : 64;
 }
 
-static void pack_params_of(const gca_conv_geom* g, int which, const ClassInfo& c, size_t nclasses, PackParams& p) {
+static void pack_params_of(const gca_conv_geom* g, int which, const ClassInfo& c, const IgemmCfg& cf, PackParams& p) {
   const int T = taps(g);
-  {
-    IgemmParams ip{};
-    class_params(g, which, c, ip);
-    const IgemmCfg cf = cfg_for(g, which, c, ip, nclasses);
-    p.fmt = cf.halo; p.math = cf.math; p.SC = c.srcC; p.nsteps = cf.halo == 2 ? cf.kt_per_split : cdiv(c.srcC, 16) * c.ntaps;
-  }
+  p.fmt = (int)cf.kernel; p.math = cf.math; p.SC = c.srcC;
+  p.nsteps = cf.kernel == ConvKernel::Stem ? cf.kt_per_split : cdiv(c.srcC, 16) * c.ntaps;
   const bool pwfmt = p.fmt == 3;
   p.Kred = (int)c.Kred; p.M = c.M; p.Kpad = pwfmt ? (int)gca_round_up(c.srcC, 32) : (int)c.Kpad; p.Mrows = pack_rows(c.M);
   p.ntaps = p.fmt == 2 ? g->kd * g->kh : c.ntaps; p.nb = c.nb; p.nc = c.nc;       // (stem pack: reduction rows per channel)
@@ -1333,15 +1355,15 @@ static void pack_params_of(const gca_conv_geom* g, int which, const ClassInfo& c
 
 int64_t gca_conv_pack_jobs_host(const gca_conv_geom* g, int which, const float* w, float* packed, void* jobs_out) {
   if (!geom_ok(g) || (which != 0 && which != 1)) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
+  const ConvLaunch L = resolve_launch(g, which);
   int64_t n = 0;
-  for (const ClassInfo& c : cls) {
+  for (size_t i = 0; i < L.cls.size(); ++i) {
+    const ClassInfo& c = L.cls[i];
     if (c.ntaps == 0) continue;
     if (jobs_out) {
       if (!w || !packed) return GCA_EINVAL;
       PackJob j{};
-      pack_params_of(g, which, c, cls.size(), j.p);
+      pack_params_of(g, which, c, L.cf[i], j.p);
       j.w = w; j.packed = packed + c.pack_off;
       j.first_block = 0;
       j.nblocks = (int)gca_ceil_div(pack_items(j.p), PACK_CHUNK);
@@ -1378,12 +1400,12 @@ int gca_conv_pack_batched(const void* jobs_dev, int64_t njobs, int64_t total_blo
 
 int gca_conv_pack(const gca_conv_geom* g, int which, const float* w, float* packed, void* stream) {
   if (!geom_ok(g) || (which != 0 && which != 1) || !w || !packed) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
-  for (const ClassInfo& c : cls) {
+  const ConvLaunch L = resolve_launch(g, which);
+  for (size_t i = 0; i < L.cls.size(); ++i) {
+    const ClassInfo& c = L.cls[i];
     if (c.ntaps == 0) continue;
     PackParams p{};
-    pack_params_of(g, which, c, cls.size(), p);
+    pack_params_of(g, which, c, L.cf[i], p);
     long long blocks = gca_ceil_div(pack_items(p), 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w,
@@ -1395,10 +1417,8 @@ int gca_conv_pack(const gca_conv_geom* g, int which, const float* w, float* pack
 int64_t gca_conv_table_rows(const gca_conv_geom* g, int which) {
   if (!geom_ok(g) || which < 0 || which > 2) return GCA_EINVAL;
   if (which == 2) return gca_round_up((int64_t)g->C * taps(g) + TABLE_PAD_W, 64);   // any wgrad tile (<= 192 wide) stays inside
-  std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
   int64_t n = 0;
-  for (const ClassInfo& c : cls) if (c.ntaps) n += c.Kpad + 32;
+  for (const ClassInfo& c : resolve_launch(g, which).cls) if (c.ntaps) n += c.Kpad + 32;
   return n > 0 ? n : 32;
 }
 
@@ -1420,12 +1440,11 @@ int gca_conv_table_build_host(const gca_conv_geom* g, int which, int32_t* t) {
     }
     return GCA_OK;
   }
-  std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
+  const ConvLaunch L = resolve_launch(g, which);
   const int64_t SHW = which == 0 ? HW : (int64_t)g->OH * g->OW;
   const int64_t SW = which == 0 ? g->W : g->OW;
   const int64_t SDHW = which == 0 ? DHW : SHW * g->OD;
-  for (const ClassInfo& c : cls) {
+  for (const ClassInfo& c : L.cls) {
     if (c.ntaps == 0) continue;
     int32_t* rows = t + 2 * c.table_off;
     for (int64_t k = 0; k < c.Kpad; ++k) {
@@ -1454,18 +1473,15 @@ int gca_conv_table_build_host(const gca_conv_geom* g, int which, int32_t* t) {
 
 int64_t gca_conv_pack_layout(const gca_conv_geom* g, int which) {
   if (!geom_ok(g) || which < 0 || which > 1) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
+  const ConvLaunch L = resolve_launch(g, which);
   int64_t sig = 0;
-  for (const ClassInfo& c : cls) {
-    int code = 0;                                  // 0: k-major fp32 rows; 4 + arithmetic: LDS-halo layout; 1..3: stem layout
-    if (c.ntaps) {
-      IgemmParams p{};
-      class_params(g, which, c, p);
-      const IgemmCfg cf = cfg_for(g, which, c, p, cls.size());
-      if (cf.halo == 3) code = 8;                   // pointwise fp16 GEMM operand
-      else if (cf.halo == 2) code = cf.math;        // stem layout (arithmetic 1..3)
-      else if (cf.halo) code = 4 + cf.math;
+  for (const IgemmCfg& cf : L.cf) {
+    int code = 0;                                  // 0: k-major fp32 rows (also: a class with no taps)
+    switch (cf.kernel) {
+      case ConvKernel::Gather: break;
+      case ConvKernel::Halo: code = 4 + cf.math; break;          // LDS-halo layout
+      case ConvKernel::Stem: code = cf.math; break;              // stem layout (arithmetic 1..3)
+      case ConvKernel::Pointwise: code = 8; break;               // pointwise fp16 GEMM operand
     }
     sig = sig * 16 + code;
     if (sig > (1LL << 56)) sig %= 1000000007LL;    // (more than 14 classes: a hash is enough)
@@ -1475,14 +1491,14 @@ int64_t gca_conv_pack_layout(const gca_conv_geom* g, int which) {
 
 int gca_conv_kernel_cfg(const gca_conv_geom* g, int which, int32_t* out4) {
   if (!geom_ok(g) || which < 0 || which > 1 || !out4) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, which, cls);
-  for (const ClassInfo& c : cls) {
+  const ConvLaunch L = resolve_launch(g, which);
+  for (size_t i = 0; i < L.cls.size(); ++i) {          // the first class with taps
+    const ClassInfo& c = L.cls[i];
+    const IgemmCfg& cf = L.cf[i];
     if (c.ntaps == 0) continue;
-    IgemmParams p{};
-    class_params(g, which, c, p);
-    const IgemmCfg cf = cfg_for(g, which, c, p, cls.size());
-    out4[0] = cf.bm; out4[1] = cf.bn; out4[2] = cf.splits; out4[3] = (int)cls.size() | (fast_of(c.ntaps) << 8) | (c.vec << 10) | (cf.math << 12) | ((cf.halo == 1) << 14) | (cf.h << 15) | ((cf.halo == 2) << 16) | ((cf.halo == 3) << 17);
+    out4[0] = cf.bm; out4[1] = cf.bn; out4[2] = cf.splits;
+    out4[3] = (int)L.cls.size() | (fast_of(c.ntaps) << 8) | (c.vec << 10) | (cf.math << 12) | ((cf.kernel == ConvKernel::Halo) << 14) |
+              (cf.h << 15) | ((cf.kernel == ConvKernel::Stem) << 16) | ((cf.kernel == ConvKernel::Pointwise) << 17);
     return GCA_OK;
   }
   return GCA_EINVAL;
@@ -1490,13 +1506,10 @@ int gca_conv_kernel_cfg(const gca_conv_geom* g, int which, int32_t* out4) {
 
 int64_t gca_conv_fwd_stat_parts(const gca_conv_geom* g) {
   if (!geom_ok(g)) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, 0, cls);
-  IgemmParams p{};
-  class_params(g, 0, cls[0], p);
-  const IgemmCfg cf = cfg_for(g, 0, cls[0], p, 1);
-  if (cf.halo == 3) return (int64_t)g->N * cdiv((int)((long long)g->OD * g->OH * g->OW), 128);
-  return stat_parts(cf, p.Ntot, cf.halo ? halo_tiles_n(g, cls[0], cf) : 0);
+  const ConvLaunch L = resolve_launch(g, 0);
+  const IgemmCfg& cf = L.cf[0];
+  if (cf.kernel == ConvKernel::Pointwise) return (int64_t)g->N * cdiv((int)((long long)g->OD * g->OH * g->OW), 128);
+  return stat_parts(cf, L.p[0].Ntot, cf.kernel != ConvKernel::Gather ? halo_tiles_n(g, L.cls[0], cf) : 0);
 }
 
 int64_t gca_conv_fwd_ws_bytes(const gca_conv_geom* g) { return geom_ok(g) ? ws_bytes_for(g, 0) : GCA_EINVAL; }
@@ -1509,43 +1522,30 @@ int gca_conv_fwd(const gca_conv_geom* g, const void* x_, const float* wpack, con
   float* y = reinterpret_cast<float*>(y_);
   if (!geom_ok(g) || !x || !wpack || !table || !y) return GCA_EINVAL;
   if ((stat_sum == nullptr) != (stat_sq == nullptr)) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, 0, cls);
-  const ClassInfo& c = cls[0];
-  IgemmParams p{};
-  class_params(g, 0, c, p);
-  p.accumulate = 0;
-  const IgemmCfg cf = cfg_for(g, 0, c, p, 1);
-  if (cf.halo == 3) return run_class_pw(g, 0, x, wpack, bias, y, stat_sum, stat_sq, p, (hipStream_t)stream);
-  if (cf.halo == 2) return run_class_stem(g, cf, x, wpack, bias, y, stat_sum, stat_sq, p, (hipStream_t)stream);
-  if (cf.halo)
-    return run_class_halo(g, c, cf, x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum, stat_sq,
-                          reinterpret_cast<float*>(ws), p, (hipStream_t)stream);
-  return run_class(cf, fast_of(c.ntaps), x, wpack, reinterpret_cast<const int2*>(table), bias,
-                   y, stat_sum, stat_sq, reinterpret_cast<float*>(ws), p, (hipStream_t)stream);
+  return run_resolved_class(g, 0, resolve_launch(g, 0), 0, x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum,
+                            stat_sq, reinterpret_cast<float*>(ws), 0, (hipStream_t)stream);
 }
 
 int gca_conv_fwd_slabs(const gca_conv_geom* g, const void* x, const float* wpack, const int32_t* table, void* ws,
                        int32_t* out_splits, void* stream) {
-  if (!out_splits || !ws || !geom_ok(g) || g->act_f16) return GCA_EINVAL;
-  t_leave_slabs = true; t_left_splits = 0;
-  // (y is never written in this mode; the pointer only has to be non-null for the argument check)
-  const int rc = gca_conv_fwd(g, x, wpack, table, nullptr, ws, nullptr, nullptr, ws, stream);
-  t_leave_slabs = false;
+  if (!out_splits || !ws || !x || !wpack || !table || !geom_ok(g) || g->act_f16) return GCA_EINVAL;
+  const ConvLaunch L = resolve_launch(g, 0);
+  const IgemmCfg& cf = L.cf[0];
+  // only split-K launches of the gather / halo kernels leave slabs: anything else is refused before a launch (the caller
+  // must use gca_conv_fwd)
+  if ((cf.kernel != ConvKernel::Gather && cf.kernel != ConvKernel::Halo) || cf.splits < 2) return GCA_EINVAL;
+  float* slab = reinterpret_cast<float*>(ws);           // (the destination is never written in this mode)
+  const int rc = run_resolved_class(g, 0, L, 0, reinterpret_cast<const float*>(x), wpack, reinterpret_cast<const int2*>(table),
+                                    nullptr, slab, nullptr, nullptr, slab, 0, (hipStream_t)stream, true);
   if (rc) return rc;
-  if (t_left_splits < 2) return GCA_EINVAL;             // this launch shape does not split: the caller must use gca_conv_fwd
-  *out_splits = t_left_splits;
+  *out_splits = cf.splits;
   return GCA_OK;
 }
 
 int gca_conv_xf_ok(const gca_conv_geom* g) {
   if (!geom_ok(g) || g->act_f16) return 0;
-  std::vector<ClassInfo> cls;
-  build_classes(g, 0, cls);
-  IgemmParams p{};
-  class_params(g, 0, cls[0], p);
-  const IgemmCfg cf = cfg_for(g, 0, cls[0], p, 1);
-  if (cf.halo != 1 || cf.math == 3) return 0;
+  const IgemmCfg cf = resolve_launch(g, 0).cf[0];
+  if (cf.kernel != ConvKernel::Halo || cf.math == 3) return 0;
   const int wm = resolve_math(g->tune_wgrad_math, 0);
   return g->tune_wgrad_tile >= 11 && g->tune_wgrad_tile <= 12 && wgrad_ts_ok(g, g->tune_wgrad_tile, wm) ? 1 : 0;
 }
@@ -1556,16 +1556,10 @@ int gca_conv_fwd_xf(const gca_conv_geom* g, const void* x_, const float* in_scal
   float* y = reinterpret_cast<float*>(y_);
   if (!geom_ok(g) || g->act_f16 || !x || !in_scale || !in_shift || !wpack || !table || !y) return GCA_EINVAL;
   if ((stat_sum == nullptr) != (stat_sq == nullptr)) return GCA_EINVAL;
-  std::vector<ClassInfo> cls;
-  build_classes(g, 0, cls);
-  const ClassInfo& c = cls[0];
-  IgemmParams p{};
-  class_params(g, 0, c, p);
-  p.accumulate = 0;
-  const IgemmCfg cf = cfg_for(g, 0, c, p, 1);
-  if (cf.halo != 1) return GCA_EINVAL;                 // only the LDS-halo kernels stage their input through registers
-  return run_class_halo(g, c, cf, x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum, stat_sq,
-                        reinterpret_cast<float*>(ws), p, (hipStream_t)stream, in_scale, in_shift);
+  const ConvLaunch L = resolve_launch(g, 0);
+  if (L.cf[0].kernel != ConvKernel::Halo) return GCA_EINVAL;    // only the LDS-halo kernels stage their input through registers
+  return run_resolved_class(g, 0, L, 0, x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum, stat_sq,
+                            reinterpret_cast<float*>(ws), 0, (hipStream_t)stream, false, in_scale, in_shift);
 }
 
 int gca_conv_dgrad(const gca_conv_geom* g, const void* dy_, const float* wpack, const int32_t* table,
@@ -1575,10 +1569,9 @@ int gca_conv_dgrad(const gca_conv_geom* g, const void* dy_, const float* wpack, 
   if (!geom_ok(g) || !dy || !wpack || !table || !dx) return GCA_EINVAL;
   if (g->x_batch_stride != 0 && g->x_batch_stride != (long long)g->C * g->D * g->H * g->W) return GCA_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  std::vector<ClassInfo> cls;
-  build_classes(g, 1, cls);
+  const ConvLaunch L = resolve_launch(g, 1);
   bool any_empty = false;
-  for (const ClassInfo& c : cls) any_empty |= c.ntaps == 0;
+  for (const ClassInfo& c : L.cls) any_empty |= c.ntaps == 0;
   if (any_empty && !accumulate) {          // positions no tap reaches (e.g. 1x1x1 stride 2) get an exact zero
     const long long n = (long long)g->N * g->C * g->D * g->H * g->W;
     const long long n32 = g->act_f16 ? n / 2 : n;                 // dx holds n elements of 2 (fp16 storage) or 4 bytes
@@ -1588,17 +1581,11 @@ int gca_conv_dgrad(const gca_conv_geom* g, const void* dy_, const float* wpack, 
                        g->act_f16 ? (int)(n & 1) : 0);
   }
   const int2* tab = reinterpret_cast<const int2*>(table);
-  for (const ClassInfo& c : cls) {
+  for (size_t i = 0; i < L.cls.size(); ++i) {
+    const ClassInfo& c = L.cls[i];
     if (c.ntaps == 0) continue;
-    IgemmParams p{};
-    class_params(g, 1, c, p);
-    p.accumulate = accumulate ? 1 : 0;
-    const IgemmCfg cf = cfg_for(g, 1, c, p, cls.size());
-    int rc = cf.halo == 3 ? run_class_pw(g, 1, dy, wpack + c.pack_off, nullptr, dx, nullptr, nullptr, p, st)
-           : cf.halo ? run_class_halo(g, c, cf, dy, wpack + c.pack_off, tab + c.table_off, nullptr, dx, nullptr, nullptr,
-                                      reinterpret_cast<float*>(ws), p, st)
-                     : run_class(cf, fast_of(c.ntaps), dy, wpack + c.pack_off,
-                                 tab + c.table_off, nullptr, dx, nullptr, nullptr, reinterpret_cast<float*>(ws), p, st);
+    const int rc = run_resolved_class(g, 1, L, i, dy, wpack + c.pack_off, tab + c.table_off, nullptr, dx, nullptr, nullptr,
+                                      reinterpret_cast<float*>(ws), accumulate, st);
     if (rc) return rc;
   }
   return GCA_OK;

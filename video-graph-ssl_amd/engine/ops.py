@@ -134,6 +134,18 @@ def _time_ms(fn, reps=3):
     return a.elapsed_time(b) / reps
 
 
+# Flags of a forward / dgrad tune code (gca_conv_geom.tune_fwd_bm / tune_dgrad_bm; the low bits are the tile rows, 32..160)
+TUNE_VEC = 1024      # 256-column float4 variant of the gather kernels
+TUNE_HALO = 2048     # LDS-halo kernel (conv3d_halo.hip), box in tune_*_box
+TUNE_STEM = 4096     # stem kernel (conv3d_stem.hip), forward only
+TUNE_PW = 8192       # pointwise fp16 GEMM kernel (conv3d_pw.hip)
+
+
+def _tune_kernel(code):
+    """Kernel family a tune code asks for (as named by ConvPlan.kernel)."""
+    return 'halo' if code & TUNE_HALO else 'stem' if code & TUNE_STEM else 'pw' if code & TUNE_PW else 'gather'
+
+
 class ConvPlan:
     """Everything geometry-dependent about one conv: the ABI struct, device gather tables, and the launch
     configuration pinned by a one-off measurement (the role cudnn.benchmark plays in the reference)."""
@@ -182,6 +194,12 @@ class ConvPlan:
         else:
             H.call('gca_conv_kernel_cfg', self.gp, which, out)
         return tuple(out)
+
+    def kernel(self, which):
+        """Kernel family the forward (0) / dgrad (1) pass runs on under the configuration in force: 'gather', 'halo',
+        'stem' or 'pw' (bits 14 / 16 / 17 of gca_conv_kernel_cfg's last word)."""
+        kc = self.cfg(which)[3]
+        return 'halo' if kc >> 14 & 1 else 'stem' if kc >> 16 & 1 else 'pw' if kc >> 17 & 1 else 'gather'
 
     WGRAD_SHAPES = {1: (64, 64), 2: (64, 128), 3: (128, 64), 4: (128, 128), 5: (96, 128), 6: (160, 128), 7: (128, 96),
                     8: (128, 160), 9: (64, 192), 10: (192, 64)}
@@ -234,12 +252,12 @@ class ConvPlan:
 
     # ---- one-off launch tuning ------------------------------------------------------------
     def _igemm_candidates(self, M, Ntot, kred):
-        """(tile code, split) pairs: tile code = rows (32..160) | 1024 for the 256-column float4 variant."""
+        """(tile code, split) pairs: tile code = rows (32..160) | TUNE_VEC for the 256-column float4 variant."""
         nk = -(-kred // 16)
         g = self.g
         pointwise = g.kh == 1 and g.kw == 1 and g.sh == 1 and g.sw == 1 and g.ph == 0 and g.pw == 0
         cands = []
-        for vec in ((0, 1024) if pointwise else (0,)):
+        for vec in ((0, TUNE_VEC) if pointwise else (0,)):
             bn = 256 if vec else 128
             for bm in (32, 64, 96, 128, 160):
                 padded = -(-M // bm) * bm
@@ -253,7 +271,7 @@ class ConvPlan:
         return cands
 
     def _halo_candidates(self, which, M):
-        """LDS-halo kernel candidates (tile code | 2048, split, box code): the few boxes with the least padding of the
+        """LDS-halo kernel candidates (tile code | TUNE_HALO, split, box code): the few boxes with the least padding of the
         output grid x halo size, each with the tile heights that pad M least.  Unit-stride dgrad and forward only."""
         g = self.g
         if which == 0:
@@ -294,7 +312,7 @@ class ConvPlan:
                 if cost > 2.0:
                     continue
                 for bm in rows:
-                    out.append((bm | 2048, 1, b[0] | (b[1] << 8) | (b[2] << 16)))
+                    out.append((bm | TUNE_HALO, 1, b[0] | (b[1] << 8) | (b[2] << 16)))
         return out
 
     def tune(self, which, run, repack=None):
@@ -314,16 +332,10 @@ class ConvPlan:
 
         def apply(c):
             # igemm: (tile code, splits, tail code, math code, box code); wgrad: (tile shape, splits, math code); short = zeros
-            if which == 0:
-                g.tune_fwd_bm, g.tune_fwd_splits = c[0], c[1]
-                g.tune_fwd_tail = c[2] if len(c) > 2 else 0
-                g.tune_fwd_math = c[3] if len(c) > 3 else 0
-                g.tune_fwd_box = c[4] if len(c) > 4 else 0
-            elif which == 1:
-                g.tune_dgrad_bm, g.tune_dgrad_splits = c[0], c[1]
-                g.tune_dgrad_tail = c[2] if len(c) > 2 else 0
-                g.tune_dgrad_math = c[3] if len(c) > 3 else 0
-                g.tune_dgrad_box = c[4] if len(c) > 4 else 0
+            if which < 2:
+                pass_ = ('fwd', 'dgrad')[which]
+                for field, v in zip(('bm', 'splits', 'tail', 'math', 'box'), tuple(c) + (0,) * (5 - len(c))):
+                    setattr(g, 'tune_%s_%s' % (pass_, field), v)
             else:
                 g.tune_wgrad_tile, g.tune_wgrad_splits = c[0], c[1]
                 g.tune_wgrad_math = c[2] if len(c) > 2 else 0
@@ -354,14 +366,14 @@ class ConvPlan:
             cands = [c + (0,) for c in self._igemm_candidates(K, N * OD * OH * OW, g.C * self.taps)]
             cands += self._halo_candidates(0, K)
             if g.C <= 4 and g.sw == 2 and g.kw <= 8:
-                cands.append((4096 | 64, 1, 0))                   # stem kernel (conv3d_stem.hip), box by its own heuristic
+                cands.append((TUNE_STEM | 64, 1, 0))              # stem kernel (conv3d_stem.hip), box by its own heuristic
             if g.act_f16 and self.taps == 1:
-                cands.append((8192 | 128, 1, 0))                  # pointwise fp16 GEMM kernel (conv3d_pw.hip)
+                cands.append((TUNE_PW | 128, 1, 0))               # pointwise fp16 GEMM kernel (conv3d_pw.hip)
         elif which == 1:
             cands = [c + (0,) for c in self._igemm_candidates(g.C, g.N * g.D * g.H * g.W, K * self.taps)]
             cands += self._halo_candidates(1, g.C)
             if g.act_f16 and self.taps == 1:
-                cands.append((8192 | 128, 1, 0))
+                cands.append((TUNE_PW | 128, 1, 0))
         else:
             cands = self._wgrad_candidates(K, g.C * self.taps, -(-(N * OD * OH * OW) // 32))
         # The arithmetic mode is a floor on accuracy: a pass may run a MORE accurate kernel when that one is faster
@@ -375,9 +387,7 @@ class ConvPlan:
             if which == 2 and self.cfg(2)[3] & 255 != c[0]:      # shape not available for this tap count
                 return None
             if which < 2:
-                kc = self.cfg(which)[3]
-                if (bool(c[0] & 2048) != bool((kc >> 14) & 1) or bool(c[0] & 4096) != bool((kc >> 16) & 1)
-                        or bool(c[0] & 8192) != bool((kc >> 17) & 1)):
+                if self.kernel(which) != _tune_kernel(c[0]):
                     return None                                   # halo / stem kernel asked for but not runnable here (or vice versa)
                 if layout() != packed_as[0]:
                     if repack is None:
@@ -405,7 +415,7 @@ class ConvPlan:
             tilesN = -(-Ntot // 128)
             for _, base in list(timed[:2]):
                 bm, sp, m = base[0], base[1], base[3]
-                if not single_class or sp != 1 or bm >= 1024 or bm <= 32:
+                if not single_class or sp != 1 or bm >= TUNE_VEC or bm <= 32:
                     continue
                 tilesM = -(-M // bm)
                 seen = set()
