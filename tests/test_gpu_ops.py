@@ -319,23 +319,23 @@ def test_conv_math_mode_is_a_floor_on_accuracy(ops):
         dw_f32 = torch.zeros_like(w); ops.conv_wgrad(plan, x, dy, dw_f32, accumulate=True)
         plan.g.tune_fwd_math = plan.g.tune_wgrad_math = 2          # bf16x3 asked for, f32 in force: ignored
         plan.refresh()
-        assert (plan.cfg(0)[3] >> 12) & 3 == 0 and (plan.cfg(2)[3] >> 12) & 3 == 0
+        assert plan.math(0) == 0 and plan.math(2) == 0
         assert torch.equal(ops.conv_fwd(plan, x, wp), y_f32)
         ops.set_conv_math('bf16x3')
         plan.g.tune_fwd_math = plan.g.tune_wgrad_math = 0
         plan.refresh()
-        assert (plan.cfg(0)[3] >> 12) & 3 == 1 and (plan.cfg(2)[3] >> 12) & 3 == 1
+        assert plan.math(0) == 1 and plan.math(2) == 1
         e3 = rel_err(ops.conv_fwd(plan, x, wp), y_f32)
         assert 1e-7 < e3 < 5e-5
         plan.g.tune_fwd_math = plan.g.tune_wgrad_math = 1          # fp32 MFMA pinned inside bf16x3 mode
         plan.refresh()
-        assert (plan.cfg(0)[3] >> 12) & 3 == 0 and (plan.cfg(2)[3] >> 12) & 3 == 0
+        assert plan.math(0) == 0 and plan.math(2) == 0
         assert torch.equal(ops.conv_fwd(plan, x, wp), y_f32)
         dw = torch.zeros_like(w); ops.conv_wgrad(plan, x, dy, dw, accumulate=True)
         assert torch.equal(dw, dw_f32)
         plan.g.tune_fwd_math = 3                                    # bf16x6 inside bf16x3 mode
         plan.refresh()
-        assert (plan.cfg(0)[3] >> 12) & 3 == 2
+        assert plan.math(0) == 2
         assert rel_err(ops.conv_fwd(plan, x, wp), y_f32) < e3
     finally:
         ops.set_conv_math(default)
@@ -923,12 +923,12 @@ def test_conv_wgrad_streaming_temporal_kernel(ops, shape, K, kd, pd):
                 xin = xd if view else xd.contiguous()
                 plan = ops.ConvPlan(N, C, D, Hh, W, K, (kd, 1, 1), 1, (pd, 0, 0), DEV, x_batch_stride=xin.stride(0) if view else 0)
                 plan.tuned = [True, True, True]
-                for tile in (11, 12):
+                for tile, kernel in ((11, 'temporal32'), (12, 'temporal64')):
                     for sp in sorted({1, 2, max(1, units // 8), max(1, units // 4)}):
                         plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = tile, sp
                         plan.refresh()
                         cfg = plan.cfg(2)
-                        assert cfg[3] & 255 == tile, (tile, cfg)                       # really the streaming kernel
+                        assert plan.kernel(2) == kernel, (tile, cfg)                  # really the streaming kernel
                         dw = torch.full_like(w, 0.5).to(DEV)
                         ops.conv_wgrad(plan, xin, dyd, dw, accumulate=True)
                         assert rel_err(dw - 0.5, wr.grad) < tol, (mode, view, tile, sp, cfg)
@@ -939,7 +939,7 @@ def test_conv_wgrad_streaming_temporal_kernel(ops, shape, K, kd, pd):
         plan.tuned = [True, True, True]
         plan.g.tune_wgrad_tile = 11
         plan.refresh()
-        assert plan.cfg(2)[3] & 255 != 11                                              # falls back to a conv_wgrad_kernel shape
+        assert plan.kernel(2) != 'temporal32'                                          # falls back to a conv_wgrad_kernel shape
         dw = torch.zeros_like(w).to(DEV)
         ops.conv_wgrad(plan, xd.contiguous(), dyd, dw, accumulate=True)
         assert rel_err(dw, wr.grad) < 1e-5
@@ -985,7 +985,7 @@ def test_conv_wgrad_streaming_spatial_kernel(ops, shape, K):
                     plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = 13, sp
                     plan.refresh()
                     cfg = plan.cfg(2)
-                    assert cfg[3] & 255 == 13, cfg
+                    assert plan.kernel(2) == 'spatial', cfg
                     dw = torch.full_like(w, 0.5).to(DEV)
                     ops.conv_wgrad(plan, xin, dyd, dw, accumulate=True)
                     assert rel_err(dw - 0.5, wr.grad) < tol, (mode, view, sp, cfg)
@@ -996,7 +996,7 @@ def test_conv_wgrad_streaming_spatial_kernel(ops, shape, K):
             plan = ops.ConvPlan(*shp, 32, (1, 3, 3), s, (0, 1, 1), DEV)
             plan.g.tune_wgrad_tile = 13
             plan.refresh()
-            assert plan.cfg(2)[3] & 255 != 13
+            assert plan.kernel(2) != 'spatial'
     finally:
         ops.set_conv_math(default)
 
@@ -1045,7 +1045,7 @@ def test_conv_wgrad_stem_kernel(ops, shape, K, k, p):
                     plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = 14, sp
                     plan.refresh()
                     cfg = plan.cfg(2)
-                    assert cfg[3] & 255 == 14, cfg
+                    assert plan.kernel(2) == 'stem', cfg
                     dw = torch.full_like(w, 0.5).to(DEV)
                     ops.conv_wgrad(plan, xin, dyd, dw, accumulate=True)
                     assert rel_err(dw - 0.5, ref) < tol, (mode, view, sp, cfg)
@@ -1058,7 +1058,7 @@ def test_conv_wgrad_stem_kernel(ops, shape, K, k, p):
             plan = ops.ConvPlan(*shp, 32, kk, s, pp, DEV)
             plan.g.tune_wgrad_tile = 14
             plan.refresh()
-            assert plan.cfg(2)[3] & 255 != 14
+            assert plan.kernel(2) != 'stem'
     finally:
         ops.set_conv_math(default)
 
@@ -1130,7 +1130,7 @@ def test_conv_consumes_producer_batchnorm_relu_on_the_fly(ops, shape, K, kd, pd)
             plan.g.tune_fwd_bm, plan.g.tune_fwd_box = 64 | 2048, box[0] | (box[1] << 8) | (box[2] << 16)
             plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = 11, 2
             plan.refresh()
-            assert plan.kernel(0) == 'halo' and plan.cfg(2)[3] & 255 == 11
+            assert plan.kernel(0) == 'halo' and plan.kernel(2) == 'temporal32'
             assert ops.conv_xf_ok(plan)
             wp = ops.conv_pack(plan, 0, w)
             o1, (s1, q1) = ops.conv_fwd(plan, z, wp, None, stats=True)

@@ -402,6 +402,55 @@ def test_conv_launch_plans_match_the_golden_dump(pkg):
         H.lib.gca_set_conv_math(default)
 
 
+# Operand byte offsets (x, dy) of the dummy-pointer gca_conv_wgrad_partial calls of a wgrad launch-plan record; each pair is
+# tried without and with an input transform (in_scale / in_shift).
+WGRAD_OPERAND_OFFSETS = tuple((ox, oy) for ox in (0, 4, 2) for oy in (0, 4, 2))    # 16-, 4- and 2-byte aligned
+
+
+def conv_wgrad_launch_record(H, row):
+    """Everything the host side derives for one weight gradient (geometry, tune codes, arithmetic mode): gca_conv_wgrad_cfg,
+    work-space bytes, whether the fused-input path applies, gather-table rows and a digest of the table, and the status of
+    gca_conv_wgrad_partial for each operand alignment of WGRAD_OPERAND_OFFSETS -- dummy pointers on a null stream, so -1 is a
+    refusal and -2 an attempted launch (only meaningful where no kernel can run)."""
+    import ctypes as C
+    import hashlib
+    g = H.ConvGeom(*[int(v) for v in row[:len(CONV_GEOM_FIELDS)]])
+    assert H.lib.gca_set_conv_math(int(row[-1])) == 0
+    gp = C.byref(g)
+    cfg = (C.c_int32 * 4)()
+    out = [H.lib.gca_conv_wgrad_cfg(gp, cfg)] + list(cfg)
+    out += [H.lib.gca_conv_wgrad_ws_bytes(gp), H.lib.gca_conv_xf_ok(gp)]
+    rows = H.lib.gca_conv_table_rows(gp, 2)
+    tab = (C.c_int32 * (2 * max(rows, 0)))()
+    out += [rows, H.lib.gca_conv_table_build_host(gp, 2, tab),
+            int.from_bytes(hashlib.sha256(bytes(tab)).digest()[:8], 'little', signed=True)]
+    base, splits = 1 << 20, C.c_int32(0)
+    for ox, oy in WGRAD_OPERAND_OFFSETS:
+        for xf in (None, base):
+            out.append(H.lib.gca_conv_wgrad_partial(gp, base + ox, xf, xf, base + oy, base, base, C.addressof(splits), None))
+    return out
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='dummy operand pointers: only meaningful where nothing can run')
+def test_conv_wgrad_launch_plans_match_the_golden_dump(pkg):
+    """Host logic only, no kernel can run: for every geometry of profiles/tune_cache.json (its pinned tune codes and the
+    all-zero heuristic, arithmetic modes 0 / 1 / 2, fp16 storage where it was tuned), plus forced tile, split and arithmetic
+    codes, the weight-gradient launch plan -- kernel, tile, splits, arithmetic, work-space, gather table, fused-input
+    eligibility and the operand alignments each kernel accepts -- is the recorded one."""
+    for knob in ('GCA_HALO', 'GCA_PW', 'GCA_STEM'):
+        if os.environ.get(knob):
+            pytest.skip('%s changes the forward launch choice gca_conv_xf_ok depends on' % knob)
+    z = np.load(os.path.join(ROOT, 'tests', 'golden', 'conv_wgrad_launch.npz'))
+    H = pkg._hip
+    default = H.lib.gca_get_conv_math()
+    try:
+        for row, want in zip(z['inputs'], z['outputs']):
+            got = conv_wgrad_launch_record(H, row)
+            assert got == want.tolist(), dict(zip(CONV_GEOM_FIELDS + ('math',), row.tolist()))
+    finally:
+        H.lib.gca_set_conv_math(default)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='dummy operand pointers: only meaningful where nothing can run')
 def test_conv_fwd_slabs_refuses_non_split_launches_before_launching(pkg):
     """gca_conv_fwd_slabs leaves split-K slabs, so a pass whose resolved launch does not split (or runs a kernel without

@@ -51,7 +51,7 @@ def main():
             plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = tile, sp
             plan.refresh()
             cfg = plan.cfg(2)
-            if tile and cfg[3] & 255 != tile:
+            if tile and plan.kernel(2) != 'stem':
                 print('%-11s %-30s refused' % (name, label))
                 continue
             dw = torch.zeros((K, C) + k, device=DEV)
@@ -67,7 +67,7 @@ def main():
         for tile in (0, 14):
             plan2.g.tune_wgrad_tile, plan2.g.tune_wgrad_splits = tile, 7
             plan2.refresh()
-            if tile and plan2.cfg(2)[3] & 255 != tile:
+            if tile and plan2.kernel(2) != 'stem':
                 continue
             dw = torch.zeros((K, C) + k, device=DEV)
             ops._conv_wgrad_launch(plan2, x[:nn].contiguous(), dy[:nn].contiguous(), dw, False)

@@ -58,7 +58,7 @@ def main():
                 sp = max(1, min(units // 4, -(-nb // tiles)))
                 plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = tile, sp
                 plan.refresh()
-                if plan.cfg(2)[3] & 255 != tile:
+                if plan.kernel(2) != plan.WGRAD_KERNELS[tile]:
                     continue
                 rows.append(('ts tile %d splits %d (blocks %d)' % (tile, plan.cfg(2)[2], plan.cfg(2)[2] * tiles),
                              time_ms(lambda: ops._conv_wgrad_launch(plan, x, dy, dw, False))))
@@ -86,7 +86,7 @@ def spatial():
             sp = max(1, min(units // 4, nb // tiles))
             plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = 13, sp
             plan.refresh()
-            if plan.cfg(2)[3] & 255 != 13:
+            if plan.kernel(2) != 'spatial':
                 continue
             rows.append(('ss tile 13 splits %d (blocks %d)' % (plan.cfg(2)[2], plan.cfg(2)[2] * tiles),
                          time_ms(lambda: ops._conv_wgrad_launch(plan, x, dy, dw, False))))

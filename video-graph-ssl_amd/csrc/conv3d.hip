@@ -916,7 +916,7 @@ inline bool pw_geometry(const gca_conv_geom* g, int which, const IgemmParams& ip
   pw.src_nstride = (unsigned)ip.src_nstride;
   pw.src_bytes = ip.src_bytes; pw.dst_bytes = ip.dst_bytes;
   const long long pb = (long long)pack_rows(DK) * pw.Kpad * 2;
-  pw.pack_bytes = pb > 0xfffff000LL ? 0xfffff000u : (unsigned)pb;
+  pw.pack_bytes = clamp_buf_bytes(pb);
   return true;
 }
 
@@ -974,7 +974,7 @@ inline bool stem_geometry(const gca_conv_geom* g, const IgemmParams& p, int math
   sp.rowoff_bytes = (int)gca_round_up((2 * nsteps + g->C * sp.hd * sp.hh) * 4, 16);
   sp.cs_bytes = (unsigned)((long long)g->D * g->H * g->W * (g->act_f16 ? 2 : 4));
   const long long pb = (long long)nsteps * sp.Mrows * (math == 3 ? 32 : (math == 2 ? 96 : 64));
-  sp.pack_bytes = pb > 0xfffff000LL ? 0xfffff000u : (unsigned)pb;
+  sp.pack_bytes = clamp_buf_bytes(pb);
   sp.m_w2 = gca_make_magic((unsigned)sp.wp); sp.m_hdh = gca_make_magic((unsigned)(sp.hd * sp.hh));
   sp.m_hh = gca_make_magic((unsigned)sp.hh);
   return true;
@@ -1010,7 +1010,7 @@ inline bool halo_geometry(const ClassInfo& c, const IgemmParams& p, int bd, int 
   hp.Mrows = pack_rows(c.M);
   const long long cs = (long long)p.SD * p.SH * p.SW * (math == 3 ? 2 : 4);
   const long long pk = (long long)hp.nchunks * c.ntaps * hp.Mrows * halo_row_bytes(math);
-  if (cs > 0x7fffffffLL || pk > 0xfffff000LL) return false;
+  if (cs > 0x7fffffffLL || pk > BUF_MAX_BYTES) return false;
   hp.cs_bytes = (unsigned)cs;
   hp.pack_bytes = (unsigned)pk;
   return true;
@@ -1546,8 +1546,7 @@ int gca_conv_xf_ok(const gca_conv_geom* g) {
   if (!geom_ok(g) || g->act_f16) return 0;
   const IgemmCfg cf = resolve_launch(g, 0).cf[0];
   if (cf.kernel != ConvKernel::Halo || cf.math == 3) return 0;
-  const int wm = resolve_math(g->tune_wgrad_math, 0);
-  return g->tune_wgrad_tile >= 11 && g->tune_wgrad_tile <= 12 && wgrad_ts_ok(g, g->tune_wgrad_tile, wm) ? 1 : 0;
+  return resolve_wgrad(g).xf ? 1 : 0;
 }
 
 int gca_conv_fwd_xf(const gca_conv_geom* g, const void* x_, const float* in_scale, const float* in_shift, const float* wpack,

@@ -10,6 +10,7 @@
 // out-of-window tap is an out-of-range offset and reads 0 in hardware).  K is split across workgroups into
 // fp32 partial slabs that are summed in a fixed order (deterministic).
 #include <type_traits>
+#include <utility>
 #include "conv_common.h"
 
 using namespace gca_conv;
@@ -18,24 +19,7 @@ namespace {
 
 constexpr int LDW = WBK + 4;       // LDS row pitch in floats (144 B)
 
-typedef gca_magic Magic;
-inline Magic make_magic(unsigned d) { return gca_make_magic(d); }
-
-struct WgradParams {
-  int C, D, H, W, K, OD, OH, OW;
-  int kd, kh, kw;
-  int sd, sh, sw, pd, ph, pw;
-  int Kred;                 // C*taps  (GEMM N)
-  int tilesM, tilesN, splits;
-  int kt_per_split, kt_total;
-  int chk;
-  int math;                 // arithmetic of this launch (host side only)
-  int half;                 // x and dy are fp16 in HBM (host side only)
-  unsigned Ktot;            // NB*OD*OH*OW (GEMM K) -- < 2^30
-  unsigned x_nstride;       // elements between clips of x
-  unsigned x_bytes, dy_bytes, slab_bytes;
-  Magic m_osp, m_ohw, m_ow;
-};
+struct WgradParams : WgradArgs {};    // the kernel argument (conv_common.h)
 
 // Window validity of one spatial position as a bit per tap (bit = 1: tap INSIDE the input), built from per-axis
 // bit rows: kd + kh + kw range tests instead of one test per gathered element.
@@ -627,27 +611,22 @@ __global__ void bias_grad_kernel(const float* __restrict__ dy, long long N, long
   if (threadIdx.x == 0) db[k] = accumulate ? db[k] + s : s;
 }
 
-// Tile shapes (rows = output channels, cols = C*taps).  Index = gca_conv_geom.tune_wgrad_tile (0 = heuristic).
-struct WgradShape { int bm, bn, wm, wn, tm, tn; };
+// Tile shapes (rows = output channels, cols = C*taps).  Index = gca_conv_geom.tune_wgrad_tile (0 = heuristic).  fasts: the
+// tap-mask kinds (bit FAST, wgrad_fast) the shape is instantiated for -- this table is also the launcher's (launch_shape).
+struct WgradShape { int bm, bn, wm, wn, tm, tn, fasts; };
 constexpr int N_WGRAD_SHAPES = 10;
-const WgradShape WGRAD_SHAPES[N_WGRAD_SHAPES + 1] = {
-    {0, 0, 0, 0, 0, 0},
-    {64, 64, 2, 2, 1, 1},  {64, 128, 2, 2, 1, 2},  {128, 64, 2, 2, 2, 1},  {128, 128, 2, 2, 2, 2},   // 1..4
-    {96, 128, 1, 4, 3, 1}, {160, 128, 1, 4, 5, 1}, {128, 96, 4, 1, 1, 3},  {128, 160, 4, 1, 1, 5},   // 5..8
-    {64, 192, 2, 2, 1, 3}, {192, 64, 2, 2, 3, 1}};                                                    // 9..10
+constexpr WgradShape WGRAD_SHAPES[N_WGRAD_SHAPES + 1] = {
+    {0, 0, 0, 0, 0, 0, 0},
+    {64, 64, 2, 2, 1, 1, 3},  {64, 128, 2, 2, 1, 2, 3},  {128, 64, 2, 2, 2, 1, 7},  {128, 128, 2, 2, 2, 2, 7},   // 1..4
+    {96, 128, 1, 4, 3, 1, 2}, {160, 128, 1, 4, 5, 1, 2}, {128, 96, 4, 1, 1, 3, 6},  {128, 160, 4, 1, 1, 5, 6},   // 5..8 (FAST 2: the 7x7 stem family)
+    {64, 192, 2, 2, 1, 3, 2}, {192, 64, 2, 2, 3, 1, 2}};                                                          // 9..10
 
 inline int wgrad_fast(const gca_conv_geom* g) { const int t = taps(g); return t <= 31 ? 1 : (t <= 62 ? 2 : 0); }
-inline bool wgrad_shape_ok(int idx, int fast) {
-  if (idx < 1 || idx > N_WGRAD_SHAPES) return false;
-  if (fast == 1) return true;
-  if (fast == 2) return idx == 3 || idx == 4 || idx == 7 || idx == 8;       // instantiated for the 7x7 stem family
-  return idx <= 4;
-}
+inline bool wgrad_shape_ok(int idx, int fast) { return idx >= 1 && idx <= N_WGRAD_SHAPES && (WGRAD_SHAPES[idx].fasts >> fast) & 1; }
 
-struct WgradPlan { WgradParams p; int shape; bool avec; int fast; bool bvec; int ts; };   // ts: 11 / 12 = streaming temporal kernel
-
-void wgrad_plan(const gca_conv_geom* g, WgradPlan& pl) {
-  WgradParams& p = pl.p;
+// the gather kernel: tile shape (least padded MFMA work, discounted for how well a shape amortises its gathers) and split
+void wgrad_gather_plan(const gca_conv_geom* g, WgradLaunch& L) {
+  WgradArgs& p = L.gather;
   p.C = g->C; p.D = g->D; p.H = g->H; p.W = g->W; p.K = g->K;
   p.OD = g->OD; p.OH = g->OH; p.OW = g->OW;
   p.kd = g->kd; p.kh = g->kh; p.kw = g->kw;
@@ -658,52 +637,25 @@ void wgrad_plan(const gca_conv_geom* g, WgradPlan& pl) {
   const long long cdhw = (long long)g->C * g->D * g->H * g->W;
   p.x_nstride = (unsigned)(g->x_batch_stride ? g->x_batch_stride : cdhw);
   const long long es = g->act_f16 ? 2 : 4;                       // fp16 storage of x and dy
-  const long long xb = (long long)g->N * p.x_nstride * es, yb = (long long)g->N * g->K * osp * es;
-  const long long sb = (long long)g->K * p.Kred * 4;
-  p.x_bytes = xb > 0xfffff000LL ? 0xfffff000u : (unsigned)xb;
-  p.dy_bytes = yb > 0xfffff000LL ? 0xfffff000u : (unsigned)yb;
-  p.slab_bytes = sb > 0xfffff000LL ? 0xfffff000u : (unsigned)sb;
-  p.m_osp = make_magic((unsigned)osp);
-  p.m_ohw = make_magic((unsigned)(g->OH * g->OW));
-  p.m_ow = make_magic((unsigned)g->OW);
-  pl.avec = osp % 4 == 0;
-  pl.fast = wgrad_fast(g);
-  pl.bvec = pl.avec && pl.fast == 1 && g->kh == 1 && g->kw == 1 && g->sh == 1 && g->sw == 1 && g->ph == 0 && g->pw == 0 &&
-            (g->OH * g->OW) % 4 == 0 && cdhw % 4 == 0 && p.x_nstride % 4 == 0;
+  p.x_bytes = clamp_buf_bytes((long long)g->N * p.x_nstride * es);
+  p.dy_bytes = clamp_buf_bytes((long long)g->N * g->K * osp * es);
+  p.slab_bytes = clamp_buf_bytes((long long)g->K * p.Kred * 4);
+  p.m_osp = gca_make_magic((unsigned)osp);
+  p.m_ohw = gca_make_magic((unsigned)(g->OH * g->OW));
+  p.m_ow = gca_make_magic((unsigned)g->OW);
   p.kt_total = (int)gca_ceil_div((long long)p.Ktot, WBK);
-  p.math = resolve_math(g->tune_wgrad_math, g->act_f16);
+  p.math = L.math;
   p.half = p.math == 3;
-  pl.ts = 0;
-  if (g->tune_wgrad_tile == 14 && wgrad_stem_ok(g, p.math)) {
-    // conv3d_wgrad_stem.hip: whole dW per workgroup group, split over (clip, od) units
-    pl.ts = 14;
-    pl.shape = 0;
-    p.tilesM = 1;
-    p.tilesN = 1;
-    p.splits = wgrad_stem_splits(g, g->tune_wgrad_splits);
-    p.kt_per_split = 0;
-    p.chk = 0;
-    return;
-  }
-  if (g->tune_wgrad_tile >= 11 && g->tune_wgrad_tile <= 13 && wgrad_ts_ok(g, g->tune_wgrad_tile, p.math)) {
-    // conv3d_wgrad_ts.hip: its own tiling (32*TM x 32 x all taps per wave) and split (over clip x position-chunk units)
-    pl.ts = g->tune_wgrad_tile;
-    pl.shape = 0;
-    const int tm = pl.ts == 12 ? 2 : 1;
-    p.tilesM = (int)gca_ceil_div(g->K, 32 * tm);
-    p.tilesN = (int)gca_ceil_div(g->C, 32);
-    p.splits = wgrad_ts_splits(g, pl.ts, g->tune_wgrad_splits);
-    p.kt_per_split = 0;
-    p.chk = 0;
-    return;
-  }
-  // tile shape: least padded MFMA work, discounted for how well a shape amortises its gathers
+  L.avec = osp % 4 == 0;
+  L.fast = wgrad_fast(g);
+  L.bvec = L.avec && L.fast == 1 && g->kh == 1 && g->kw == 1 && g->sh == 1 && g->sw == 1 && g->ph == 0 && g->pw == 0 &&
+           (g->OH * g->OW) % 4 == 0 && cdhw % 4 == 0 && p.x_nstride % 4 == 0;
   int best = 0;
-  if (wgrad_shape_ok(g->tune_wgrad_tile, pl.fast)) best = g->tune_wgrad_tile;
+  if (wgrad_shape_ok(g->tune_wgrad_tile, L.fast)) best = g->tune_wgrad_tile;
   else {
     double best_cost = 1e300;
     for (int i = 1; i <= N_WGRAD_SHAPES; ++i) {
-      if (!wgrad_shape_ok(i, pl.fast)) continue;
+      if (!wgrad_shape_ok(i, L.fast)) continue;
       const WgradShape& sh = WGRAD_SHAPES[i];
       const double padded = (double)gca_round_up(g->K, sh.bm) * (double)gca_round_up(p.Kred, sh.bn);
       const double eff = (sh.bm * sh.bn >= 128 * 96 ? 1.0 : (sh.bm * sh.bn >= 64 * 128 ? 0.92 : 0.8)) *
@@ -712,7 +664,7 @@ void wgrad_plan(const gca_conv_geom* g, WgradPlan& pl) {
       if (cost < best_cost) { best_cost = cost; best = i; }
     }
   }
-  pl.shape = best;
+  L.shape = best;
   const WgradShape& sh = WGRAD_SHAPES[best];
   p.tilesM = (int)gca_ceil_div(g->K, sh.bm);
   p.tilesN = (int)gca_ceil_div(p.Kred, sh.bn);
@@ -728,71 +680,84 @@ void wgrad_plan(const gca_conv_geom* g, WgradPlan& pl) {
   p.chk = ((g->pd > 0 || (g->OD - 1) * g->sd + g->kd > g->D) ? 1 : 0) |
           ((g->ph > 0 || (g->OH - 1) * g->sh + g->kh > g->H) ? 2 : 0) |
           ((g->pw > 0 || (g->OW - 1) * g->sw + g->kw > g->W) ? 4 : 0);
+  L.kernel = WgradKernel::Gather;
+  L.splits = p.splits;
+  L.blocks = tiles * p.splits;
+  L.lds = 0;
+  L.x_align = L.dy_align = 1;      // the float4 forms are chosen per launch from the pointers
+  L.xf = false;
 }
 
-template <int WM, int WN, int TM, int TN, int FAST, int MATH>
+template <int WM, int WN, int TM, int TN, int FAST, int MATH, bool H = false>
 void launch_wm(int avec, dim3 grid, hipStream_t st, const float* x, const float* dy, const int2* t, float* slab,
                const WgradParams& p) {      // avec: 0 scalar, 1 float4 dY, 2 float4 dY and X
-  if (avec == 2 && FAST == 1)
-    hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, true, FAST == 1 ? 1 : 1, true, MATH>), grid, dim3(256), 0, st, x, dy, t, slab, p);
-  else if (avec) hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, true, FAST, false, MATH>), grid, dim3(256), 0, st, x, dy, t, slab, p);
-  else hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, false, FAST, false, MATH>), grid, dim3(256), 0, st, x, dy, t, slab, p);
+  if (FAST == 1 && avec == 2)
+    hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, true, 1, true, MATH, H>), grid, dim3(256), 0, st, x, dy, t, slab, p);
+  else if (avec) hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, true, FAST, false, MATH, H>), grid, dim3(256), 0, st, x, dy, t, slab, p);
+  else hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, false, FAST, false, MATH, H>), grid, dim3(256), 0, st, x, dy, t, slab, p);
 }
 
 template <int WM, int WN, int TM, int TN, int FAST>
 void launch_w(int avec, dim3 grid, hipStream_t st, const float* x, const float* dy, const int2* t, float* slab,
               const WgradParams& p) {
-  if (p.half) {
-    if (avec == 2 && FAST == 1)
-      hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, true, 1, true, 3, true>), grid, dim3(256), 0, st, x, dy, t, slab, p);
-    else if (avec) hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, true, FAST, false, 3, true>), grid, dim3(256), 0, st, x, dy, t, slab, p);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, TM, TN, false, FAST, false, 3, true>), grid, dim3(256), 0, st, x, dy, t, slab, p);
-  } else if (p.math == 1) launch_wm<WM, WN, TM, TN, FAST, 1>(avec, grid, st, x, dy, t, slab, p);
+  if (p.half) launch_wm<WM, WN, TM, TN, FAST, 3, true>(avec, grid, st, x, dy, t, slab, p);
+  else if (p.math == 1) launch_wm<WM, WN, TM, TN, FAST, 1>(avec, grid, st, x, dy, t, slab, p);
   else if (p.math == 2) launch_wm<WM, WN, TM, TN, FAST, 2>(avec, grid, st, x, dy, t, slab, p);
   else launch_wm<WM, WN, TM, TN, FAST, 0>(avec, grid, st, x, dy, t, slab, p);
 }
 
-template <int FAST>
-int launch_shape(int shape, int avec, dim3 grid, hipStream_t st, const float* x, const float* dy, const int2* t,
-                 float* slab, const WgradParams& p) {
-  switch (shape) {
-    case 1: if (FAST != 2) { launch_w<2, 2, 1, 1, FAST == 2 ? 1 : FAST>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-    case 2: if (FAST != 2) { launch_w<2, 2, 1, 2, FAST == 2 ? 1 : FAST>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-    case 3: launch_w<2, 2, 2, 1, FAST>(avec, grid, st, x, dy, t, slab, p); return 0;
-    case 4: launch_w<2, 2, 2, 2, FAST>(avec, grid, st, x, dy, t, slab, p); return 0;
-    case 5: if (FAST == 1) { launch_w<1, 4, 3, 1, 1>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-    case 6: if (FAST == 1) { launch_w<1, 4, 5, 1, 1>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-    case 7: if (FAST != 0) { launch_w<4, 1, 1, 3, FAST == 0 ? 1 : FAST>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-    case 8: if (FAST != 0) { launch_w<4, 1, 1, 5, FAST == 0 ? 1 : FAST>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-    case 9: if (FAST == 1) { launch_w<2, 2, 1, 3, 1>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-    case 10: if (FAST == 1) { launch_w<2, 2, 3, 1, 1>(avec, grid, st, x, dy, t, slab, p); return 0; } break;
-  }
+// shape S of WGRAD_SHAPES with tap-mask kind `fast`: instantiated for the kinds of its `fasts` only
+template <int S>
+int launch_shape(int fast, int avec, dim3 grid, hipStream_t st, const float* x, const float* dy, const int2* t, float* slab,
+                 const WgradParams& p) {
+  constexpr WgradShape sh = WGRAD_SHAPES[S];
+  if constexpr ((sh.fasts & 1) != 0) if (fast == 0) { launch_w<sh.wm, sh.wn, sh.tm, sh.tn, 0>(avec, grid, st, x, dy, t, slab, p); return 0; }
+  if constexpr ((sh.fasts & 2) != 0) if (fast == 1) { launch_w<sh.wm, sh.wn, sh.tm, sh.tn, 1>(avec, grid, st, x, dy, t, slab, p); return 0; }
+  if constexpr ((sh.fasts & 4) != 0) if (fast == 2) { launch_w<sh.wm, sh.wn, sh.tm, sh.tn, 2>(avec, grid, st, x, dy, t, slab, p); return 0; }
   return GCA_EINVAL;
 }
 
+template <int... S>
+int launch_gather(std::integer_sequence<int, S...>, const WgradLaunch& L, int avec, const float* x, const float* dy,
+                  const int2* t, float* slab, hipStream_t st) {
+  const WgradParams p{L.gather};
+  const dim3 grid((unsigned)L.blocks);
+  int rc = GCA_EINVAL;
+  ((L.shape == S ? (void)(rc = launch_shape<S>(L.fast, avec, grid, st, x, dy, t, slab, p)) : (void)0), ...);
+  if (rc) return rc;
+  return gca_launch_status();
+}
+
 }  // namespace
+
+WgradLaunch gca_conv::resolve_wgrad(const gca_conv_geom* g) {
+  WgradLaunch L{};
+  L.math = resolve_math(g->tune_wgrad_math, g->act_f16);
+  const int tile = g->tune_wgrad_tile;
+  if (tile == 14 && wgrad_stem_plan(g, L)) return L;                  // whole dW per workgroup group, split over (clip, od) units
+  if (tile >= 11 && tile <= 13 && wgrad_ts_plan(g, (WgradKernel)tile, L)) return L;   // split over (clip, position chunk) units
+  wgrad_gather_plan(g, L);
+  return L;
+}
 
 extern "C" {
 
 int64_t gca_conv_wgrad_ws_bytes(const gca_conv_geom* g) {
   if (!geom_ok(g)) return GCA_EINVAL;
-  WgradPlan pl{};
-  wgrad_plan(g, pl);
-  return (int64_t)pl.p.splits * g->K * pl.p.Kred * (int64_t)sizeof(float);
+  return (int64_t)resolve_wgrad(g).splits * g->K * g->C * taps(g) * (int64_t)sizeof(float);
 }
 
 /* out4 = {tile rows, tile cols, split-K factor, shape index | float4-dY<<8 | tap-mask kind<<9} */
 int gca_conv_wgrad_cfg(const gca_conv_geom* g, int32_t* out4) {
   if (!geom_ok(g) || !out4) return GCA_EINVAL;
-  WgradPlan pl{};
-  wgrad_plan(g, pl);
-  if (pl.ts) {
-    out4[0] = pl.ts == 12 ? 64 : 32; out4[1] = 32 * taps(g); out4[2] = pl.p.splits;
-    out4[3] = pl.ts | (pl.p.math << 12);
+  const WgradLaunch L = resolve_wgrad(g);
+  if (L.kernel != WgradKernel::Gather) {
+    out4[0] = L.kernel == WgradKernel::Temporal64 ? 64 : 32; out4[1] = 32 * taps(g); out4[2] = L.splits;
+    out4[3] = (int)L.kernel | (L.math << 12);
     return GCA_OK;
   }
-  out4[0] = WGRAD_SHAPES[pl.shape].bm; out4[1] = WGRAD_SHAPES[pl.shape].bn; out4[2] = pl.p.splits;
-  out4[3] = pl.shape | (pl.avec << 8) | (pl.fast << 9) | (pl.bvec << 11) | (pl.p.math << 12);
+  out4[0] = WGRAD_SHAPES[L.shape].bm; out4[1] = WGRAD_SHAPES[L.shape].bn; out4[2] = L.splits;
+  out4[3] = L.shape | (L.avec << 8) | (L.fast << 9) | (L.bvec << 11) | (L.math << 12);
   return GCA_OK;
 }
 
@@ -802,35 +767,19 @@ static int wgrad_partial_launch(const gca_conv_geom* g, const void* x_, const vo
   const float* x = reinterpret_cast<const float*>(x_);      // opaque to the host side: the kernels index in bytes
   const float* dy = reinterpret_cast<const float*>(dy_);
   if (!geom_ok(g) || !x || !dy || !table || !ws) return GCA_EINVAL;
-  WgradPlan pl{};
-  wgrad_plan(g, pl);
-  const WgradParams& p = pl.p;
-  const long long nblk = (long long)p.tilesM * p.tilesN * p.splits;
-  if (nblk > 0x7fffffffLL) return GCA_EINVAL;
-  const int2* t = reinterpret_cast<const int2*>(table);
+  const WgradLaunch L = resolve_wgrad(g);
+  if (L.blocks > 0x7fffffffLL) return GCA_EINVAL;
+  if ((in_scale && !L.xf) || (uintptr_t)x % L.x_align || (uintptr_t)dy % L.dy_align) return GCA_EINVAL;
   float* slab = reinterpret_cast<float*>(ws);
-  dim3 grid((unsigned)nblk);
   int rc;
-  if (pl.ts == 14) {
-    if (in_scale || ((uintptr_t)x % 4) || ((uintptr_t)dy % 16)) return GCA_EINVAL;
-    rc = wgrad_stem_launch(g, p.math, p.splits, x_, dy_, slab, st);
-    return rc ? rc : p.splits;
+  if (L.kernel == WgradKernel::Stem) rc = wgrad_stem_run(L, x_, dy_, slab, st);
+  else if (L.kernel != WgradKernel::Gather) rc = wgrad_ts_run(g, L, x, dy, slab, st, in_scale, in_shift);
+  else {
+    const int av = !L.avec || ((uintptr_t)dy % 16) ? 0 : (L.bvec && ((uintptr_t)x % 16) == 0 ? 2 : 1);
+    rc = launch_gather(std::make_integer_sequence<int, N_WGRAD_SHAPES + 1>(), L, av, x, dy, reinterpret_cast<const int2*>(table),
+                       slab, st);
   }
-  if (pl.ts) {
-    // 16-byte DMA pieces; rows of the (1,3,3) kernel start at arbitrary columns anyway, so only dword alignment matters there
-    if (pl.ts != 13 && (((uintptr_t)x % 16) || ((uintptr_t)dy % 16))) return GCA_EINVAL;
-    if (((uintptr_t)x % 4) || ((uintptr_t)dy % 4)) return GCA_EINVAL;
-    rc = wgrad_ts_launch(g, pl.ts, p.math, p.splits, x, dy, slab, st, in_scale, in_shift);
-    return rc ? rc : p.splits;
-  }
-  if (in_scale) return GCA_EINVAL;                       // only the streaming kernels transform x on the fly (gca_conv_xf_ok)
-  const int av = !pl.avec || ((uintptr_t)dy % 16) ? 0 : (pl.bvec && ((uintptr_t)x % 16) == 0 ? 2 : 1);
-  if (pl.fast == 1) rc = launch_shape<1>(pl.shape, av, grid, st, x, dy, t, slab, p);
-  else if (pl.fast == 2) rc = launch_shape<2>(pl.shape, av, grid, st, x, dy, t, slab, p);
-  else rc = launch_shape<0>(pl.shape, av, grid, st, x, dy, t, slab, p);
-  if (rc) return rc;
-  rc = gca_launch_status();
-  return rc ? rc : p.splits;
+  return rc ? rc : L.splits;
 }
 
 int gca_conv_wgrad(const gca_conv_geom* g, const void* x_, const void* dy_, const int32_t* table,

@@ -40,26 +40,7 @@ constexpr int CT = 5;            // column tiles of 32 per tap plane: KH * C * K
 constexpr int NB = 3;            // B fragments of a wave: its two block columns and the fifth column
 constexpr int NT = 5;            // accumulator tiles of a wave: (r0, c0) (r0, c0+1) (r0+1, c0) (r0+1, c0+1) (r0 + half, 4)
 
-struct StwParams {
-  int K, C, D, H, W, OD, OH, OW, KD, KH, KW, pd, ph, pw;
-  int nrt;                       // row tiles of 32 output channels per workgroup: 2 or 4
-  int g;                         // tap planes per workgroup: 2 when KD > 1 and nrt = 2, else 1
-  int wk;                        // waves sharing a tile set, interleaved over the steps: 2 when KD = 1 and nrt = 2, else 1
-  int ngroups;                   // ceil(KD / g)
-  int units, ups, splits;        // unit = (clip, od, chunk of ohl output rows); units per split
-  int ohc, ohl;                  // row chunks per (clip, od), rows per chunk
-  int steps;                     // ceil(OW / 16)
-  int SS, nstg;                  // steps per dY stage, stages per output row
-  int ncols;                     // KH * C * KW
-  int LQ;                        // dwords of one array: 8 * steps + 1 (odd: consecutive arrays walk all banks)
-  int ARRB, RS, PLS, ZB;         // bytes: one array, one row slot (C * NP * 4 arrays), one plane (RING slots), zero region
-  int DYB;                       // bytes of one dY stage buffer
-  int ntask;                     // staging tasks of a round: 2 * C * g * LQ
-  unsigned x_nstride, dy_nstride;   // elements between clips
-  unsigned osp;                  // OD * OH * OW
-  unsigned x_bytes, dy_bytes, slab_bytes;
-  long long nW;                  // elements of dW (slab stride)
-};
+struct StwParams : StwArgs {};    // the kernel argument (conv_common.h)
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -415,7 +396,7 @@ void stw_partition(const gca_conv_geom* g, int want, int& ohc, int& ohl, int& un
   splits = (int)gca_ceil_div(un, ups);
 }
 
-bool stw_params(const gca_conv_geom* g, int math, int want, StwParams& p, size_t& lds) {
+bool stw_params(const gca_conv_geom* g, int math, StwArgs& p, size_t& lds) {
   const int np = math == 2 ? 3 : (math == 1 ? 2 : 1);
   const int es = math == 3 ? 2 : 4;
   p.K = g->K; p.C = g->C; p.D = g->D; p.H = g->H; p.W = g->W; p.OD = g->OD; p.OH = g->OH; p.OW = g->OW;
@@ -425,7 +406,7 @@ bool stw_params(const gca_conv_geom* g, int math, int want, StwParams& p, size_t
   p.wk = p.nrt == 2 && p.g == 1 ? 2 : 1;
   p.ngroups = (int)gca_ceil_div(g->kd, p.g);
   if ((long long)g->N * g->OD * g->OH > 0x3fffffffLL) return false;
-  stw_partition(g, want, p.ohc, p.ohl, p.units, p.ups, p.splits);
+  stw_partition(g, g->tune_wgrad_splits, p.ohc, p.ohl, p.units, p.ups, p.splits);
   p.steps = (int)gca_ceil_div(g->OW, 16);
   p.ncols = g->kh * g->C * g->kw;
   p.LQ = 8 * p.steps + 1;
@@ -447,7 +428,7 @@ bool stw_params(const gca_conv_geom* g, int math, int want, StwParams& p, size_t
   p.dy_nstride = (unsigned)((long long)g->K * osp);
   p.osp = (unsigned)osp;
   const long long xb = (long long)g->N * p.x_nstride * es, yb = (long long)g->N * p.dy_nstride * es;
-  if (xb > 0xfffff000LL || yb > 0xfffff000LL) return false;          // 32-bit byte offsets
+  if (xb > BUF_MAX_BYTES || yb > BUF_MAX_BYTES) return false;        // 32-bit byte offsets
   p.x_bytes = (unsigned)xb; p.dy_bytes = (unsigned)yb;
   p.nW = (long long)g->K * g->C * g->kd * g->kh * g->kw;
   p.slab_bytes = 0;
@@ -462,10 +443,9 @@ bool stw_params(const gca_conv_geom* g, int math, int want, StwParams& p, size_t
 
 namespace gca_conv {
 
-// tune_wgrad_tile 14
-bool wgrad_stem_ok(const gca_conv_geom* g, int math) {
-  if (math < 1 || math > 3) return false;
-  if ((math == 3) != (g->act_f16 != 0)) return false;
+bool wgrad_stem_plan(const gca_conv_geom* g, WgradLaunch& L) {
+  if (L.math < 1 || L.math > 3) return false;
+  if ((L.math == 3) != (g->act_f16 != 0)) return false;
   if (g->C > 4 || g->K > 128) return false;
   if (g->sd != 1 || g->sh != 2 || g->sw != 2) return false;
   if (g->kh > RING - 2 || g->kw > 8 || g->kd > 8) return false;
@@ -475,25 +455,22 @@ bool wgrad_stem_ok(const gca_conv_geom* g, int math) {
   if (g->kw - 1 - g->pw > 3) return false;                           //        s <= 1
   if (g->W % 2 != 0 || g->OW % 8 != 0) return false;
   if (g->ph > 3) return false;                                        // zeroed row slots: rows -ph .. -1 next to 7 live ones
-  StwParams p; size_t lds;
-  return stw_params(g, math, 0, p, lds);
+  if (!stw_params(g, L.math, L.stw, L.lds)) return false;
+  L.kernel = WgradKernel::Stem;
+  L.splits = L.stw.splits;
+  L.blocks = (long long)L.stw.splits * L.stw.ngroups;
+  L.x_align = 4;
+  L.dy_align = 16;
+  L.xf = false;
+  return true;
 }
 
-int wgrad_stem_splits(const gca_conv_geom* g, int want) {
-  int ohc, ohl, units, ups, splits;
-  stw_partition(g, want, ohc, ohl, units, ups, splits);
-  return splits;
-}
-
-int wgrad_stem_launch(const gca_conv_geom* g, int math, int splits, const void* x, const void* dy, float* slab, hipStream_t st) {
-  StwParams p; size_t lds;
-  if (!stw_params(g, math, g->tune_wgrad_splits, p, lds) || p.splits != splits) return GCA_EINVAL;
-  const long long nblk = (long long)p.splits * p.ngroups;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return GCA_EINVAL;
-  const dim3 grid((unsigned)nblk);
-  if (math == 3) return launch_stw<3>(grid, lds, st, x, dy, slab, p);
-  if (math == 2) return launch_stw<2>(grid, lds, st, x, dy, slab, p);
-  return launch_stw<1>(grid, lds, st, x, dy, slab, p);
+int wgrad_stem_run(const WgradLaunch& L, const void* x, const void* dy, float* slab, hipStream_t st) {
+  const StwParams p{L.stw};
+  const dim3 grid((unsigned)L.blocks);
+  if (L.math == 3) return launch_stw<3>(grid, L.lds, st, x, dy, slab, p);
+  if (L.math == 2) return launch_stw<2>(grid, L.lds, st, x, dy, slab, p);
+  return launch_stw<1>(grid, L.lds, st, x, dy, slab, p);
 }
 
 }  // namespace gca_conv

@@ -28,21 +28,7 @@ using namespace gca_conv;
 
 namespace {
 
-struct TsParams {
-  int K, C, D, OD, HW, pd;
-  int Kred;                      // C * KD
-  int tilesM, tilesC, splits;
-  int units, units_per_split;    // unit = (clip, chunk of 16 positions)
-  int chunks;                    // HW / 16
-  int S;                         // steps per unit, padded to a multiple of KD
-  unsigned x_nstride, dy_nstride;   // elements between clips
-  unsigned x_bytes, dy_bytes, slab_bytes;
-  gca_magic m_chunks;
-  // optional input transform: x stands for relu(x * in_scale[c] + in_shift[c]) (the producer's BatchNorm + ReLU, never
-  // materialised); a lane's fragment row IS a channel, so the pair sits in two registers for the whole kernel
-  const float* in_scale;
-  const float* in_shift;
-};
+struct TsParams : TsArgs {};    // the kernel argument (conv_common.h)
 
 constexpr int PF = 4;            // ring depth (steps of DMA in flight: PF - 1 behind the one being read)
 
@@ -317,16 +303,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_ts_kernel(const float* __restr
 // an all-ones offset / an empty buffer descriptor and lands in LDS as zeros.  So all nine taps are always multiplied (the
 // two padding rows cost 2 / (3 H) of the MFMAs) and the step body has no branches: products are issued interleaved over
 // the nine accumulators.
-struct SsParams {
-  int K, C, D, H, W;
-  int Kred;                      // C * 9
-  int tilesM, tilesC, splits;
-  int units, units_per_split;    // unit = (clip, plane, chunk of 16 columns)
-  int chunks;                    // ceil(W / 16)
-  int S;                         // steps per unit: rows 0 .. H (one past the end), padded to a multiple of 3
-  unsigned x_nstride, dy_nstride;
-  unsigned x_bytes, dy_bytes, slab_bytes;
-};
+struct SsParams : SsArgs {};    // the kernel argument (conv_common.h)
 
 // quads of a 32-row x 6-quad B piece set: slot s = 6 r + (q ^ sw6(r)); eight / sixteen consecutive rows read distinct columns
 __device__ __forceinline__ int sw6(int r) { return ((r >> 2) ^ (r >> 3)) & 1; }
@@ -650,102 +627,98 @@ int launch_ts(int math, dim3 grid, size_t lds, hipStream_t st, const float* x, c
 
 namespace gca_conv {
 
-// tune_wgrad_tile 11 / 12: the streaming temporal kernel with 32 / 64 output channels per wave; 13: the streaming (1,3,3) kernel
-bool wgrad_ts_ok(const gca_conv_geom* g, int tile, int math) {
-  if (tile == 13) {
-    if (math != 1 && math != 2) return false;
-    if (g->act_f16) return false;
-    if (g->kd != 1 || g->kh != 3 || g->kw != 3 || g->sd != 1 || g->sh != 1 || g->sw != 1) return false;
+bool wgrad_ts_plan(const gca_conv_geom* g, WgradKernel kernel, WgradLaunch& L) {
+  if (L.math != 1 && L.math != 2) return false;
+  if (g->act_f16) return false;
+  const long long cdhw = (long long)g->C * g->D * g->H * g->W;
+  const unsigned x_nstride = (unsigned)(g->x_batch_stride ? g->x_batch_stride : cdhw);
+  const int tm = kernel == WgradKernel::Temporal64 ? 2 : 1;
+  const long long tiles = gca_ceil_div(g->K, 32 * tm) * gca_ceil_div(g->C, 32);
+  // split over units: ~2 workgroups' worth of blocks per CU by default, every wave of a workgroup gets a unit
+  auto split = [&](long long units, int& ups, int& splits) {
+    long long s = g->tune_wgrad_splits > 0 ? g->tune_wgrad_splits : gca_ceil_div(512, tiles);
+    if (s > units / 4) s = units / 4;
+    if (s < 1) s = 1;
+    ups = (int)gca_ceil_div(units, s);
+    splits = (int)gca_ceil_div(units, ups);
+  };
+  if (kernel == WgradKernel::Spatial) {
+    if (g->kd != 1 || g->kh != 3 || g->kw != 3 || !unit_stride(g)) return false;
     if (g->pd != 0 || g->ph != 1 || g->pw != 1) return false;
     if (g->H < 2) return false;
     if (g->W % 4 != 0 && g->W > 16) return false;                 // whole quads outside the row, or ONE chunk per row with its tail masked
+    SsArgs& p = L.ss;
+    p.K = g->K; p.C = g->C; p.D = g->D; p.H = g->H; p.W = g->W;
+    p.Kred = g->C * 9;
+    p.tilesM = (int)gca_ceil_div(g->K, 32);
+    p.tilesC = (int)gca_ceil_div(g->C, 32);
+    p.chunks = (int)gca_ceil_div(g->W, 16);
+    p.units = g->N * g->D * p.chunks;
+    split(p.units, p.units_per_split, p.splits);
+    p.S = (int)gca_round_up(g->H + 1, 3);
+    p.x_nstride = x_nstride;
+    p.dy_nstride = (unsigned)((long long)g->K * g->D * g->H * g->W);
+    p.x_bytes = clamp_buf_bytes((long long)g->N * p.x_nstride * 4);
+    p.dy_bytes = clamp_buf_bytes((long long)g->N * p.dy_nstride * 4);
+    p.slab_bytes = clamp_buf_bytes((long long)g->K * p.Kred * 4);
+    const size_t ring = (size_t)4 * PF * (2 + 3) * 1024, red = (size_t)2 * 9 * 16 * 64 * 4;
+    L.kernel = kernel;
+    L.splits = p.splits;
+    L.blocks = (long long)p.tilesM * p.tilesC * p.splits;
+    L.lds = ring > red ? ring : red;
+    L.x_align = L.dy_align = 4;      // rows start at arbitrary columns anyway: only dword alignment matters
+    L.xf = false;
     return true;
   }
-  if (tile != 11 && tile != 12) return false;
-  if (math != 1 && math != 2) return false;
-  if (g->act_f16) return false;
-  if (g->kh != 1 || g->kw != 1 || g->sd != 1 || g->sh != 1 || g->sw != 1 || g->ph != 0 || g->pw != 0) return false;
+  if (kernel != WgradKernel::Temporal32 && kernel != WgradKernel::Temporal64) return false;
+  if (g->kh != 1 || g->kw != 1 || !unit_stride(g) || g->ph != 0 || g->pw != 0) return false;
   if (g->kd != 3 && g->kd != 7) return false;
   if (g->pd > g->kd - 1) return false;
   if ((g->H * g->W) % 16 != 0) return false;
-  return true;
-}
-
-int wgrad_ts_splits(const gca_conv_geom* g, int tile, int want) {
-  const int tm = tile == 12 ? 2 : 1;
-  const long long tiles = gca_ceil_div(g->K, 32 * tm) * gca_ceil_div(g->C, 32);
-  const long long units = tile == 13 ? (long long)g->N * g->D * gca_ceil_div(g->W, 16) : (long long)g->N * (g->H * g->W / 16);
-  long long s = want > 0 ? want : gca_ceil_div(512, tiles);   // ~2 workgroups' worth of blocks per CU by default
-  if (s > units / 4) s = units / 4;                           // every wave of a workgroup gets a unit
-  if (s < 1) s = 1;
-  const long long ups = gca_ceil_div(units, s);
-  return (int)gca_ceil_div(units, ups);
-}
-
-static int wgrad_ss_launch(const gca_conv_geom* g, int math, int splits, const float* x, const float* dy, float* slab, hipStream_t st) {
-  SsParams p;
-  p.K = g->K; p.C = g->C; p.D = g->D; p.H = g->H; p.W = g->W;
-  p.Kred = g->C * 9;
-  p.tilesM = (int)gca_ceil_div(g->K, 32);
-  p.tilesC = (int)gca_ceil_div(g->C, 32);
-  p.chunks = (int)gca_ceil_div(g->W, 16);
-  p.units = g->N * g->D * p.chunks;
-  p.units_per_split = (int)gca_ceil_div(p.units, splits);
-  p.splits = (int)gca_ceil_div(p.units, p.units_per_split);
-  if (p.splits != splits) return GCA_EINVAL;
-  p.S = (int)gca_round_up(g->H + 1, 3);
-  const long long cdhw = (long long)g->C * g->D * g->H * g->W;
-  p.x_nstride = (unsigned)(g->x_batch_stride ? g->x_batch_stride : cdhw);
-  p.dy_nstride = (unsigned)((long long)g->K * g->D * g->H * g->W);
-  const long long xb = (long long)g->N * p.x_nstride * 4, yb = (long long)g->N * p.dy_nstride * 4;
-  const long long sb = (long long)g->K * p.Kred * 4;
-  p.x_bytes = xb > 0xfffff000LL ? 0xfffff000u : (unsigned)xb;
-  p.dy_bytes = yb > 0xfffff000LL ? 0xfffff000u : (unsigned)yb;
-  p.slab_bytes = sb > 0xfffff000LL ? 0xfffff000u : (unsigned)sb;
-  const long long nblk = (long long)p.tilesM * p.tilesC * p.splits;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return GCA_EINVAL;
-  const size_t ring = (size_t)4 * PF * (2 + 3) * 1024;
-  const size_t red = (size_t)2 * 9 * 16 * 64 * 4;
-  if (g->W % 4) return launch_ss<1, true>(math, dim3((unsigned)nblk), ring > red ? ring : red, st, x, dy, slab, p);
-  return launch_ss<1, false>(math, dim3((unsigned)nblk), ring > red ? ring : red, st, x, dy, slab, p);
-}
-
-int wgrad_ts_launch(const gca_conv_geom* g, int tile, int math, int splits, const float* x, const float* dy, float* slab,
-                    hipStream_t st, const float* in_scale, const float* in_shift) {
-  if (tile == 13) return in_scale ? GCA_EINVAL : wgrad_ss_launch(g, math, splits, x, dy, slab, st);
-  const int tm = tile == 12 ? 2 : 1;
-  TsParams p;
+  TsArgs& p = L.ts;
   p.K = g->K; p.C = g->C; p.D = g->D; p.OD = g->OD; p.HW = g->H * g->W; p.pd = g->pd;
   p.Kred = g->C * g->kd;
   p.tilesM = (int)gca_ceil_div(g->K, 32 * tm);
   p.tilesC = (int)gca_ceil_div(g->C, 32);
   p.chunks = p.HW / 16;
   p.units = g->N * p.chunks;
-  p.units_per_split = (int)gca_ceil_div(p.units, splits);
-  p.splits = (int)gca_ceil_div(p.units, p.units_per_split);
-  if (p.splits != splits) return GCA_EINVAL;
+  split(p.units, p.units_per_split, p.splits);
   const int w0 = g->kd - 1 - g->pd;
   const int s = (g->D > g->OD + w0 ? g->D : g->OD + w0);
   p.S = (int)gca_round_up(s, g->kd);
-  const long long cdhw = (long long)g->C * g->D * p.HW;
-  p.x_nstride = (unsigned)(g->x_batch_stride ? g->x_batch_stride : cdhw);
+  p.x_nstride = x_nstride;
   p.dy_nstride = (unsigned)((long long)g->K * g->OD * p.HW);
-  const long long xb = (long long)g->N * p.x_nstride * 4, yb = (long long)g->N * p.dy_nstride * 4;
-  const long long sb = (long long)g->K * p.Kred * 4;
-  p.x_bytes = xb > 0xfffff000LL ? 0xfffff000u : (unsigned)xb;
-  p.dy_bytes = yb > 0xfffff000LL ? 0xfffff000u : (unsigned)yb;
-  p.slab_bytes = sb > 0xfffff000LL ? 0xfffff000u : (unsigned)sb;
+  p.x_bytes = clamp_buf_bytes((long long)g->N * p.x_nstride * 4);
+  p.dy_bytes = clamp_buf_bytes((long long)g->N * p.dy_nstride * 4);
+  p.slab_bytes = clamp_buf_bytes((long long)g->K * p.Kred * 4);
   p.m_chunks = gca_make_magic((unsigned)p.chunks);
+  p.in_scale = p.in_shift = nullptr;
+  const size_t ring = (size_t)4 * PF * (2 * tm + 2) * 1024, red = (size_t)2 * tm * g->kd * 16 * 64 * 4;
+  L.kernel = kernel;
+  L.splits = p.splits;
+  L.blocks = (long long)p.tilesM * p.tilesC * p.splits;
+  L.lds = ring > red ? ring : red;
+  L.x_align = L.dy_align = 16;     // 16-byte DMA pieces
+  L.xf = true;
+  return true;
+}
+
+int wgrad_ts_run(const gca_conv_geom* g, const WgradLaunch& L, const float* x, const float* dy, float* slab, hipStream_t st,
+                 const float* in_scale, const float* in_shift) {
+  const dim3 grid((unsigned)L.blocks);
+  if (L.kernel == WgradKernel::Spatial) {
+    const SsParams p{L.ss};
+    if (g->W % 4) return launch_ss<1, true>(L.math, grid, L.lds, st, x, dy, slab, p);
+    return launch_ss<1, false>(L.math, grid, L.lds, st, x, dy, slab, p);
+  }
+  TsParams p{L.ts};
   p.in_scale = in_scale; p.in_shift = in_shift;
-  const long long nblk = (long long)p.tilesM * p.tilesC * p.splits;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return GCA_EINVAL;
-  const size_t ring = (size_t)4 * PF * (2 * tm + 2) * 1024;
-  const size_t red = (size_t)2 * tm * g->kd * 16 * 64 * 4;
-  const size_t lds = ring > red ? ring : red;
-  const dim3 grid((unsigned)nblk);
-  if (g->kd == 7) return tm == 2 ? launch_ts<7, 2>(math, grid, lds, st, x, dy, slab, p) : launch_ts<7, 1>(math, grid, lds, st, x, dy, slab, p);
-  if (tm == 2) return launch_ts<3, 2>(math, grid, lds, st, x, dy, slab, p);
-  return launch_ts<3, 1>(math, grid, lds, st, x, dy, slab, p);
+  if (g->kd == 7) {
+    if (L.kernel == WgradKernel::Temporal64) return launch_ts<7, 2>(L.math, grid, L.lds, st, x, dy, slab, p);
+    return launch_ts<7, 1>(L.math, grid, L.lds, st, x, dy, slab, p);
+  }
+  if (L.kernel == WgradKernel::Temporal64) return launch_ts<3, 2>(L.math, grid, L.lds, st, x, dy, slab, p);
+  return launch_ts<3, 1>(L.math, grid, L.lds, st, x, dy, slab, p);
 }
 
 }  // namespace gca_conv

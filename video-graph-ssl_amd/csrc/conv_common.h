@@ -108,15 +108,111 @@ inline bool geom_ok(const gca_conv_geom* g) {
 
 inline int taps(const gca_conv_geom* g) { return g->kd * g->kh * g->kw; }
 
-// conv3d_wgrad_ts.hip: streaming weight-gradient kernel of the unit-stride temporal convolutions (tune_wgrad_tile 11 / 12)
-bool wgrad_ts_ok(const gca_conv_geom* g, int tile, int math);
-int wgrad_ts_splits(const gca_conv_geom* g, int tile, int want);
-int wgrad_ts_launch(const gca_conv_geom* g, int tile, int math, int splits, const float* x, const float* dy, float* slab,
-                    hipStream_t st, const float* in_scale = nullptr, const float* in_shift = nullptr);
-// conv3d_wgrad_stem.hip: weight gradient of the <= 4-channel, stride-2 stem convolutions (tune_wgrad_tile 14)
-bool wgrad_stem_ok(const gca_conv_geom* g, int math);
-int wgrad_stem_splits(const gca_conv_geom* g, int want);
-int wgrad_stem_launch(const gca_conv_geom* g, int math, int splits, const void* x, const void* dy, float* slab, hipStream_t st);
+// Byte ranges of buffer resources are 32-bit: a range past BUF_MAX_BYTES is clamped to it (the kernels address < 2^30
+// elements of 4 bytes from the base, geom_ok), or refused where the whole range must be addressable.
+constexpr long long BUF_MAX_BYTES = 0xfffff000LL;
+inline unsigned clamp_buf_bytes(long long b) { return b > BUF_MAX_BYTES ? (unsigned)BUF_MAX_BYTES : (unsigned)b; }
+
+// ---- weight gradient (conv3d_wgrad*.hip) --------------------------------------------------------------------------------
+// Parameter blocks of the weight-gradient kernels.  Each kernel file takes its block by a derived type of its own
+// (WgradParams, TsParams, SsParams, StwParams: those names are part of the kernel symbols).
+
+struct WgradArgs {               // conv3d_wgrad.hip: the gather kernel
+  int C, D, H, W, K, OD, OH, OW;
+  int kd, kh, kw;
+  int sd, sh, sw, pd, ph, pw;
+  int Kred;                 // C*taps  (GEMM N)
+  int tilesM, tilesN, splits;
+  int kt_per_split, kt_total;
+  int chk;
+  int math;                 // arithmetic of this launch (host side only)
+  int half;                 // x and dy are fp16 in HBM (host side only)
+  unsigned Ktot;            // NB*OD*OH*OW (GEMM K) -- < 2^30
+  unsigned x_nstride;       // elements between clips of x
+  unsigned x_bytes, dy_bytes, slab_bytes;
+  gca_magic m_osp, m_ohw, m_ow;
+};
+
+struct TsArgs {                  // conv3d_wgrad_ts.hip: the streaming temporal kernel
+  int K, C, D, OD, HW, pd;
+  int Kred;                      // C * KD
+  int tilesM, tilesC, splits;
+  int units, units_per_split;    // unit = (clip, chunk of 16 positions)
+  int chunks;                    // HW / 16
+  int S;                         // steps per unit, padded to a multiple of KD
+  unsigned x_nstride, dy_nstride;   // elements between clips
+  unsigned x_bytes, dy_bytes, slab_bytes;
+  gca_magic m_chunks;
+  // optional input transform: x stands for relu(x * in_scale[c] + in_shift[c]) (the producer's BatchNorm + ReLU, never
+  // materialised); a lane's fragment row IS a channel, so the pair sits in two registers for the whole kernel
+  const float* in_scale;
+  const float* in_shift;
+};
+
+struct SsArgs {                  // conv3d_wgrad_ts.hip: the streaming (1,3,3) kernel
+  int K, C, D, H, W;
+  int Kred;                      // C * 9
+  int tilesM, tilesC, splits;
+  int units, units_per_split;    // unit = (clip, plane, chunk of 16 columns)
+  int chunks;                    // ceil(W / 16)
+  int S;                         // steps per unit: rows 0 .. H (one past the end), padded to a multiple of 3
+  unsigned x_nstride, dy_nstride;
+  unsigned x_bytes, dy_bytes, slab_bytes;
+};
+
+struct StwArgs {                 // conv3d_wgrad_stem.hip: the stem kernel
+  int K, C, D, H, W, OD, OH, OW, KD, KH, KW, pd, ph, pw;
+  int nrt;                       // row tiles of 32 output channels per workgroup: 2 or 4
+  int g;                         // tap planes per workgroup: 2 when KD > 1 and nrt = 2, else 1
+  int wk;                        // waves sharing a tile set, interleaved over the steps: 2 when KD = 1 and nrt = 2, else 1
+  int ngroups;                   // ceil(KD / g)
+  int units, ups, splits;        // unit = (clip, od, chunk of ohl output rows); units per split
+  int ohc, ohl;                  // row chunks per (clip, od), rows per chunk
+  int steps;                     // ceil(OW / 16)
+  int SS, nstg;                  // steps per dY stage, stages per output row
+  int ncols;                     // KH * C * KW
+  int LQ;                        // dwords of one array: 8 * steps + 1 (odd: consecutive arrays walk all banks)
+  int ARRB, RS, PLS, ZB;         // bytes: one array, one row slot (C * NP * 4 arrays), one plane (RING slots), zero region
+  int DYB;                       // bytes of one dY stage buffer
+  int ntask;                     // staging tasks of a round: 2 * C * g * LQ
+  unsigned x_nstride, dy_nstride;   // elements between clips
+  unsigned osp;                  // OD * OH * OW
+  unsigned x_bytes, dy_bytes, slab_bytes;
+  long long nW;                  // elements of dW (slab stride)
+};
+
+// Kernel family of a weight gradient.  The values are the tune_wgrad_tile codes that request the streaming kernels, which are
+// also the shape field gca_conv_wgrad_cfg reports for them.
+enum class WgradKernel { Gather = 0, Temporal32 = 11, Temporal64 = 12, Spatial = 13, Stem = 14 };
+
+// The resolved launch of one weight gradient (resolve_wgrad): every entry point reads this one plan.
+struct WgradLaunch {
+  WgradKernel kernel;
+  int math;                      // resolved arithmetic (resolve_math)
+  int splits;                    // fp32 slabs the kernel leaves (gca_conv_wgrad_ws_bytes)
+  long long blocks;              // workgroups of the launch (256 threads each)
+  size_t lds;                    // dynamic LDS bytes
+  int x_align, dy_align;         // byte alignment the kernel needs of x / dy
+  bool xf;                       // takes a pre-activation x with in_scale / in_shift (gca_conv_xf_ok)
+  // the gather kernel: tile shape index, float4 dY, tap-mask kind, float4 X
+  int shape; bool avec; int fast; bool bvec;
+  // the block of the chosen kernel; the others stay unset
+  WgradArgs gather;
+  TsArgs ts;
+  SsArgs ss;
+  StwArgs stw;
+};
+
+// conv3d_wgrad.hip (geom_ok(g) holds)
+WgradLaunch resolve_wgrad(const gca_conv_geom* g);
+// conv3d_wgrad_ts.hip: the streaming temporal (kernel Temporal32 / Temporal64) or (1,3,3) (Spatial) kernel.  Fills L (math
+// already resolved) and returns true when g can run there.
+bool wgrad_ts_plan(const gca_conv_geom* g, WgradKernel kernel, WgradLaunch& L);
+int wgrad_ts_run(const gca_conv_geom* g, const WgradLaunch& L, const float* x, const float* dy, float* slab, hipStream_t st,
+                 const float* in_scale, const float* in_shift);
+// conv3d_wgrad_stem.hip: the <= 4-channel, stride-2 stem kernel, same contract
+bool wgrad_stem_plan(const gca_conv_geom* g, WgradLaunch& L);
+int wgrad_stem_run(const WgradLaunch& L, const void* x, const void* dy, float* slab, hipStream_t st);
 inline bool unit_stride(const gca_conv_geom* g) { return g->sd == 1 && g->sh == 1 && g->sw == 1; }
 
 

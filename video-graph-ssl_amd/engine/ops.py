@@ -195,11 +195,21 @@ class ConvPlan:
             H.call('gca_conv_kernel_cfg', self.gp, which, out)
         return tuple(out)
 
+    # shape field (low byte of gca_conv_wgrad_cfg's last word) of the streaming wgrad kernels; 1..10 = the gather kernel's shapes
+    WGRAD_KERNELS = {11: 'temporal32', 12: 'temporal64', 13: 'spatial', 14: 'stem'}
+
     def kernel(self, which):
         """Kernel family the forward (0) / dgrad (1) pass runs on under the configuration in force: 'gather', 'halo',
-        'stem' or 'pw' (bits 14 / 16 / 17 of gca_conv_kernel_cfg's last word)."""
+        'stem' or 'pw' (bits 14 / 16 / 17 of gca_conv_kernel_cfg's last word); for the weight gradient (2): 'gather',
+        'temporal32', 'temporal64', 'spatial' or 'stem'."""
         kc = self.cfg(which)[3]
+        if which == 2:
+            return self.WGRAD_KERNELS.get(kc & 255, 'gather')
         return 'halo' if kc >> 14 & 1 else 'stem' if kc >> 16 & 1 else 'pw' if kc >> 17 & 1 else 'gather'
+
+    def math(self, which):
+        """Arithmetic the pass runs with (bits 12-13 of the configuration's last word): 0 f32, 1 bf16x3, 2 bf16x6, 3 fp16."""
+        return self.cfg(which)[3] >> 12 & 3
 
     WGRAD_SHAPES = {1: (64, 64), 2: (64, 128), 3: (128, 64), 4: (128, 128), 5: (96, 128), 6: (160, 128), 7: (128, 96),
                     8: (128, 160), 9: (64, 192), 10: (192, 64)}
