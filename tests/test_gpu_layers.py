@@ -99,12 +99,35 @@ def _configs1_layer_records():
     return out
 
 
+def _wgrad_fp64(x, dy, wshape, k, s, p):
+    """dw[m, c, tap] = sum_{n, o} dy[n, m, o] * x[n, c, o * s - p + tap] accumulated in fp64 (torch on the device, one
+    matrix product per clip and tap; nothing of the kernels under test)."""
+    K, C = wshape[:2]
+    (kd, kh, kw), (sd, sh, sw), (pd, ph, pw) = k, s, p
+    OD, OH, OW = dy.shape[2:]
+    out = torch.zeros((K, C, kd, kh, kw), dtype=torch.float64, device=x.device)
+    for n in range(x.shape[0]):
+        xn = F.pad(x[n].double(), (pw, pw, ph, ph, pd, pd))
+        gn = dy[n].double().reshape(K, -1)
+        for a in range(kd):
+            for b in range(kh):
+                for c in range(kw):
+                    xs = xn[:, a:a + (OD - 1) * sd + 1:sd, b:b + (OH - 1) * sh + 1:sh, c:c + (OW - 1) * sw + 1:sw]
+                    out[:, :, a, b, c] += gn @ xs.reshape(C, -1).t()
+    return out.reshape(wshape)
+
+
 @pytest.mark.parametrize('math', ['bf16x6', 'f32'])
 def test_configs1_every_layer_fwd_dgrad_wgrad_under_tuned_shapes(pkg, tuned_launch_shapes, math):
-    """All 39 GEMM layers of configs[1], each fed the oracle's own (x, dy): forward, input gradient and weight gradient
-    against the oracle's (fp32 oneDNN) results.  Bar 5e-5 max-norm per layer and pass -- two fp32-grade implementations
-    with different summation orders over up to 1.6 M products agree to ~1e-6; a wrong tile/box/class is O(1).  The bias
-    gradient of the head Linears rides along."""
+    """All 39 GEMM layers of configs[1], each fed the oracle's own (x, dy): forward and input gradient against the oracle's
+    (fp32 oneDNN) results, the weight gradient against the same sum accumulated in fp64.  Bar 5e-5 max-norm per layer and
+    pass -- a wrong tile/box/class is O(1).  The bias gradient of the head Linears rides along.
+
+    Why the weight gradient has its own reference: it sums up to 1.6 M products per element, and oneDNN's fp32 sum of them
+    depends on the host's thread count -- for conv1_t (32 x 110 x 16 x 56 x 56 -> 64, 7 taps) it is 3.0e-3 from the fp64 sum
+    with 1 thread, 3.8e-4 with 4, 1.9e-4 with 8, 8.4e-5 with 16 and 3.9e-5 with 32, i.e. above this test's bar on a host
+    with 16 threads or fewer whatever the kernel does.  The oracle's own fp32 value is still required to be the same
+    quantity (1e-2, three times its single-thread error)."""
     ops = tuned_launch_shapes
     ops.set_conv_math(math)
     recs = _configs1_layer_records()
@@ -133,9 +156,11 @@ def test_configs1_every_layer_fwd_dgrad_wgrad_under_tuned_shapes(pkg, tuned_laun
             e['dgrad'] = rel_err(dx.reshape(r['dx'].shape), r['dx'])
         dw = torch.zeros_like(w)
         ops.conv_wgrad(plan, x, dy, dw, accumulate=True)
-        e['wgrad'] = rel_err(dw.reshape(r['dw'].shape), r['dw'])
+        dw64 = _wgrad_fp64(x, dy, tuple(w.shape), r['k'], r['s'], r['p'])
+        assert rel_err(r['dw'].reshape(w.shape), dw64) < 1e-2, r['name']
+        e['wgrad'] = rel_err(dw, dw64)
         ops.conv_wgrad(plan, x, dy, dw, accumulate=True)         # += into a live gradient buffer
-        e['wgrad_acc'] = rel_err(dw.reshape(r['dw'].shape), 2 * r['dw'])
+        e['wgrad_acc'] = rel_err(dw, 2 * dw64)
         if r['db'] is not None:
             db = torch.zeros(w.shape[0], device=DEV)
             ops.bias_grad(dy, x.shape[0], w.shape[0], 1, db, True)
@@ -146,7 +171,7 @@ def test_configs1_every_layer_fwd_dgrad_wgrad_under_tuned_shapes(pkg, tuned_laun
             assert v < 5e-5, (math, r['name'], tuple(x.shape), r['k'], r['s'], key, v, plan.cfg(0), plan.cfg(1), plan.cfg(2))
             if v > worst.get(key, (0.0, ''))[0]:
                 worst[key] = (v, r['name'])
-        del x, dy, w, y, dw
+        del x, dy, w, y, dw, dw64
     assert tuned >= 30, tuned                                    # the plans really carry measured launch shapes
     print('configs[1] %s per-layer worst: %s' % (math, {k_: '%.1e @ %s' % v for k_, v in worst.items()}))
 

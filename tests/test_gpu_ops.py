@@ -531,8 +531,11 @@ def test_moco_allk_wrap_and_device_pointer(ops, golden):
 @pytest.mark.parametrize('b,K,D', [(32, 4096, 128), (5, 1000, 128), (40, 65536, 128), (70, 16384, 128), (33, 9000, 64),
                                    (8, 300, 96), (16, 2048, 136)])
 def test_infonce_sizes_vs_oracle(ops, b, K, D):
-    """BASELINE configs' InfoNCE shapes (b=32 K=4096 / 65536) + ragged sizes, vs the oracle: every workgroup width
-    of the fused kernel (1 / 2 / 4 / 8 waves), several batch tiles, narrower features, and D = 136 (two-pass path)."""
+    """BASELINE configs' InfoNCE shapes (b=32 K=4096 / 65536) + ragged sizes, vs the oracle: the single-launch persistent
+    kernel (b <= 32: 1, 2 and 4 waves), the fused kernel at 2 and 8 waves (b > 32: 33 / 70 and 40 rows, i.e. several batch
+    tiles), narrower features, and D = 136 (plain two-pass path, one wave per workgroup).  The remaining paths and widths
+    (fused with 1 / 4 waves or b <= 32, the plain 4-wave kernel, the persistent kernel with a capped grid) are selected
+    one by one in tests/test_gpu_edges.py."""
     from oracle.moco import RGBMoCo, NCESoftmaxLoss
     torch.manual_seed(6)
     mo = RGBMoCo(D, K=K, T=0.07)

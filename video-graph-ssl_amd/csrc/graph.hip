@@ -162,14 +162,14 @@ __global__ void adj_bwd_kernel(const float* dadj, const float* __restrict__ sim,
   const int i = r % T;
   const float eps = 1.1920928955078125e-07f;
   float dot = 0.f;
-  // dsim_j = dadj_j * a(1-a)/temp / (p(1-p)) * theta(h)   inside the clamp range and the hop band
+  // dsim_j = dadj_j * a(1-a)/temp / (p(1-p)) * theta(h)   inside the clamp range (bounds included) and the hop band
   for (int pass = 0; pass < 2; ++pass) {
     for (int j = 0; j < T; ++j) {
       const long long e = (long long)r * T + j;
       const int h = abs(i - j);
       float ds = 0.f;
       const float p = pre[e];
-      if (h <= max_hop && p > eps && p < 1.f - eps) {
+      if (h <= max_hop && p >= eps && p <= 1.f - eps) {      // torch.clamp's backward: the gradient passes AT a bound
         const float a = adj[e];
         ds = dadj[e] * a * (1.f - a) / temp / (p * (1.f - p)) * theta_hop(h, alpha);
       }
