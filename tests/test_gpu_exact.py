@@ -456,7 +456,7 @@ def test_f16_storage_every_kernel_family_and_split_k(ops):
     c = exact.case('fr')
     plan = _plan(ops, c, act_f16=True)
     fams = set()
-    cands = [(cc[0], cc[2]) for which in (0, 1) for cc in plan._halo_candidates(which, c.K if which == 0 else c.shape[1])]
+    cands = [(cc.bm, cc.box) for which in (0, 1) for cc in ops.tune.halo_boxes(which, plan.g)]
     for code, box, sp in [(64, 0, 1), (64, 0, 3), (128, 0, 1), (1024 + 64, 0, 1)] + [(cd, bx, sp) for cd, bx in sorted(set(cands))[::3] for sp in (1, 2)]:
         plan.g.tune_fwd_bm = plan.g.tune_dgrad_bm = code
         plan.g.tune_fwd_box = plan.g.tune_dgrad_box = box

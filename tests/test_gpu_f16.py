@@ -106,8 +106,7 @@ def test_conv_f16_every_halo_box_and_gather_tile(ops):
     yr = F.conv3d(x.double(), w.half().double(), None, s, p)
     seen = set()
     for which, name in ((0, 'fwd'), (1, 'dgrad')):
-        M = K if which == 0 else shape[1]
-        cands = [(0, 0)] + [(c[0], c[2]) for c in plan._halo_candidates(which, M)] + [(64, 0), (128, 0)]
+        cands = [(0, 0)] + [(c.bm, c.box) for c in ops.tune.halo_boxes(which, plan.g)] + [(64, 0), (128, 0)]
         ref = None
         for code, box in cands:
             setattr(plan.g, 'tune_%s_bm' % name, code)

@@ -777,6 +777,49 @@ def test_autotuner_pins_a_valid_configuration(ops):
     assert rel_err(y, yr) < 1e-5 and rel_err(dx, xr.grad) < 1e-5 and rel_err(dw, wr.grad) < 1e-5
 
 
+def test_autotuner_repacks_the_weights_between_layouts(ops, monkeypatch):
+    """The measurement above with the raw weights handed over (w_raw): the LDS-halo candidates (C >= 16, 9 taps) are measured
+    too, and the tuner re-packs the weights whenever the configuration it turns to reads another layout than the buffer
+    holds.  Same bars; and the layout the pinned configuration reads is the one the pack buffer was last written in (at this
+    shape a wrong re-pack decision shows as wrong numbers)."""
+    monkeypatch.setattr(ops, '_TUNE_CACHE', {})            # measure: the test above leaves this geometry's entries behind
+    monkeypatch.setattr(ops, '_TUNE_DIRTY', [False])
+    torch.manual_seed(6)
+    shape, K, k, s, p = (4, 24, 4, 14, 14), 72, (1, 3, 3), (1, 1, 1), (0, 1, 1)
+    x = torch.randn(shape)
+    w = torch.randn((K, shape[1]) + k) * 0.1
+    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    yr = F.conv3d(xr, wr, None, s, p)
+    dy = torch.randn_like(yr)
+    yr.backward(dy)
+    plan = ops.ConvPlan(*shape, K, k, s, p, DEV)
+    plan.tuned = [False] * 3
+    layout = lambda which: ops.H.lib.gca_conv_pack_layout(plan.gp, which)
+    wd = w.to(DEV)
+    packs = [ops.conv_pack(plan, which, wd) for which in (0, 1)]
+    written, repacks = [layout(0), layout(1)], [0, 0]
+    make_repacker = ops._repacker
+
+    def spying_repacker(plan_, which, w_raw, wpack):
+        repack = make_repacker(plan_, which, w_raw, wpack)
+
+        def spy():
+            repack()
+            written[which] = layout(which)
+            repacks[which] += 1
+        return spy
+    monkeypatch.setattr(ops, '_repacker', spying_repacker)
+    y = ops.conv_fwd(plan, x.to(DEV), packs[0], w_raw=wd)
+    dx = ops.conv_dgrad(plan, dy.to(DEV), packs[1], w_raw=wd)
+    dw = torch.zeros_like(w).to(DEV)
+    ops.conv_wgrad(plan, x.to(DEV), dy.to(DEV), dw, accumulate=True)
+    assert plan.tuned == [True, True, True]
+    g = plan.g
+    assert g.tune_fwd_bm and g.tune_dgrad_bm and g.tune_wgrad_tile and min(g.tune_fwd_splits, g.tune_dgrad_splits, g.tune_wgrad_splits) >= 1
+    assert min(repacks) >= 1 and [layout(0), layout(1)] == written, (repacks, written, layout(0), layout(1))
+    assert rel_err(y, yr) < 1e-5 and rel_err(dx, xr.grad) < 1e-5 and rel_err(dw, wr.grad) < 1e-5
+
+
 @pytest.mark.parametrize('shape,K,k,s,p', [
     ((32, 3, 16, 112, 112), 110, (1, 7, 7), (1, 2, 2), (0, 3, 3)),     # R(2+1)D-18 stem, BASELINE configs[1] size
     ((32, 110, 16, 56, 56), 64, (7, 1, 1), (1, 1, 1), (3, 0, 0)),      # stem temporal conv (158 GFLOP)

@@ -80,16 +80,15 @@ def main():
                 cfg_h[:3], t_h, flops / 1e9 / t_h, t_g, flops / 1e9 / t_g, ' '.join('%.1e' % e for e in errs))
             print(line, flush=True)
             if args.cands:
-                M = m.out_channels if which == 0 else shp[1]
-                for c in plan._halo_candidates(which, M):
-                    setattr(plan.g, 'tune_%s_bm' % name, c[0])
-                    setattr(plan.g, 'tune_%s_box' % name, c[2])
+                for c in ops.tune.halo_boxes(which, plan.g):
+                    setattr(plan.g, 'tune_%s_bm' % name, c.bm)
+                    setattr(plan.g, 'tune_%s_box' % name, c.box)
                     plan.refresh()
                     if (plan.cfg(which)[3] >> 14) & 1:
                         out_c, t_c = run(which)
                         e = max(rel(a, b) for a, b in zip(out_c, out_g))
                         print('      halo rows %3d box %s: %.3f ms %6.1f TF  diff %.1e' % (
-                            c[0] & 1023, (c[2] & 255, (c[2] >> 8) & 255, c[2] >> 16), t_c, flops / 1e9 / t_c, e), flush=True)
+                            c.bm & 1023, (c.box & 255, (c.box >> 8) & 255, c.box >> 16), t_c, flops / 1e9 / t_c, e), flush=True)
                 setattr(plan.g, 'tune_%s_bm' % name, 0)
                 setattr(plan.g, 'tune_%s_box' % name, 0)
                 plan.refresh()

@@ -40,14 +40,10 @@ def main():
         dw = torch.zeros(K, C, kd, 1, 1, device=DEV)
         flops = 2.0 * N * K * D * H * W * C * kd
         plan.tuned = [True, True, False]
-        key = [k for k in ops._TUNE_CACHE if k.startswith('v%d%s:2:' % (ops.H.lib.gca_version(), 'c'))
-               and k.endswith(','.join(str(v) for v in (N, C, D, H, W, K, kd, 1, 1, 1, 1, 1, pd, 0, 0, 0)))]
+        hit = ops._TUNE_CACHE.get(plan.tune_key(2))
         rows = []
-        if key:
-            hit = ops._TUNE_CACHE[key[0]]
-            plan.g.tune_wgrad_tile, plan.g.tune_wgrad_splits = hit[0], hit[1]
-            plan.g.tune_wgrad_math = hit[2] if len(hit) > 2 else 0
-            plan.refresh()
+        if hit:
+            plan.set_code(2, ops.tune.WgradCode(*hit))
             rows.append(('tuned conv_wgrad_kernel %s' % (plan.cfg(2)[:3],), time_ms(lambda: ops._conv_wgrad_launch(plan, x, dy, dw, False))))
         plan.g.tune_wgrad_math = 0
         units = N * (H * W // 16)

@@ -1,8 +1,10 @@
-"""Thin tensor-level wrappers over the C ABI (one function per kernel family).
+"""Tensor-level wrappers over the C ABI (one function per kernel family), and the per-geometry conv plans.
 
 torch is used for device memory and the current HIP stream only; every arithmetic
 operation below runs in libgca_hip.so.  Geometry-dependent host data (gather tables,
-workspace sizes) is cached per geometry.
+workspace sizes, the pinned launch configuration) is cached per geometry in a ConvPlan.  A plan measures its launch
+configuration once (ConvPlan.tune -> ConvPlan.search); the launch codes and the candidate lists it measures are host
+arithmetic in engine/tune.py.
 """
 import ctypes as C
 import functools
@@ -12,6 +14,8 @@ import torch
 
 from .. import _hip as H
 from .._hip import aptr, is_half, ptr, stream
+from . import tune
+from .tune import TUNE_HALO, TUNE_PW, TUNE_STEM, TUNE_VEC      # (flags of a forward / dgrad launch code; tests and tools force them)
 
 F32 = torch.float32
 F16 = torch.float16
@@ -134,16 +138,14 @@ def _time_ms(fn, reps=3):
     return a.elapsed_time(b) / reps
 
 
-# Flags of a forward / dgrad tune code (gca_conv_geom.tune_fwd_bm / tune_dgrad_bm; the low bits are the tile rows, 32..160)
-TUNE_VEC = 1024      # 256-column float4 variant of the gather kernels
-TUNE_HALO = 2048     # LDS-halo kernel (conv3d_halo.hip), box in tune_*_box
-TUNE_STEM = 4096     # stem kernel (conv3d_stem.hip), forward only
-TUNE_PW = 8192       # pointwise fp16 GEMM kernel (conv3d_pw.hip)
+# Kernel families of the forward / dgrad pass: (name, flag of a launch code's bm that asks for it, bit of gca_conv_kernel_cfg's
+# last word that reports it); neither set = the gather kernels
+_KERNELS = (('halo', TUNE_HALO, 14), ('stem', TUNE_STEM, 16), ('pw', TUNE_PW, 17))
 
 
 def _tune_kernel(code):
     """Kernel family a tune code asks for (as named by ConvPlan.kernel)."""
-    return 'halo' if code & TUNE_HALO else 'stem' if code & TUNE_STEM else 'pw' if code & TUNE_PW else 'gather'
+    return next((name for name, flag, _ in _KERNELS if code & flag), 'gather')
 
 
 class ConvPlan:
@@ -197,133 +199,38 @@ class ConvPlan:
 
     # shape field (low byte of gca_conv_wgrad_cfg's last word) of the streaming wgrad kernels; 1..10 = the gather kernel's shapes
     WGRAD_KERNELS = {11: 'temporal32', 12: 'temporal64', 13: 'spatial', 14: 'stem'}
+    WGRAD_SHAPES = tune.WGRAD_SHAPES
 
     def kernel(self, which):
         """Kernel family the forward (0) / dgrad (1) pass runs on under the configuration in force: 'gather', 'halo',
-        'stem' or 'pw' (bits 14 / 16 / 17 of gca_conv_kernel_cfg's last word); for the weight gradient (2): 'gather',
-        'temporal32', 'temporal64', 'spatial' or 'stem'."""
+        'stem' or 'pw'; for the weight gradient (2): 'gather', 'temporal32', 'temporal64', 'spatial' or 'stem'."""
         kc = self.cfg(which)[3]
         if which == 2:
             return self.WGRAD_KERNELS.get(kc & 255, 'gather')
-        return 'halo' if kc >> 14 & 1 else 'stem' if kc >> 16 & 1 else 'pw' if kc >> 17 & 1 else 'gather'
+        return next((name for name, _, bit in _KERNELS if kc >> bit & 1), 'gather')
 
     def math(self, which):
         """Arithmetic the pass runs with (bits 12-13 of the configuration's last word): 0 f32, 1 bf16x3, 2 bf16x6, 3 fp16."""
         return self.cfg(which)[3] >> 12 & 3
 
-    WGRAD_SHAPES = {1: (64, 64), 2: (64, 128), 3: (128, 64), 4: (128, 128), 5: (96, 128), 6: (160, 128), 7: (128, 96),
-                    8: (128, 160), 9: (64, 192), 10: (192, 64)}
-
-    def _wgrad_candidates(self, M, Nred, kt):
-        """(tile shape index, split) pairs.  Shapes whose padding multiplies mostly zeros are skipped; the kernel
-        refuses shapes it was not built for (the tuner then just skips them)."""
-        cands = []
-        least = min(-(-M // bm) * bm * -(-Nred // bn) * bn for bm, bn in self.WGRAD_SHAPES.values())
-        for idx, (bm, bn) in self.WGRAD_SHAPES.items():
-            padded = -(-M // bm) * bm * -(-Nred // bn) * bn
-            if padded > 1.25 * least:
-                continue
-            tiles = -(-M // bm) * -(-Nred // bn)
-            base = max(1, min(kt // 4, 1024 // max(1, tiles)))
-            for f in (0.5, 1, 2):
-                sp = max(1, min(kt, 1024, int(base * f)))
-                if sp * M * Nred * 4 > (256 << 20):
-                    continue
-                cands.append((idx, sp))
-        # the streaming temporal kernel (conv3d_wgrad_ts.hip: tile 11 = 32, 12 = 64 output channels per wave); its split
-        # is over (clip, 16-position chunk) units.  The library refuses it where it does not apply (fp32-MFMA mode, ...).
-        g = self.g
-        hw = g.H * g.W
-        if (g.kh, g.kw, g.sd, g.sh, g.sw, g.ph, g.pw) == (1, 1, 1, 1, 1, 0, 0) and g.kd in (3, 7) and hw % 16 == 0 and not g.act_f16:
-            units = g.N * (hw // 16)
-            for idx, tm in ((11, 1), (12, 2)):
-                tiles = -(-M // (32 * tm)) * -(-g.C // 32)
-                for nb in (256, 512, 1024):
-                    cands.append((idx, max(1, min(units // 4, -(-nb // tiles)))))
-        # the streaming (1,3,3) kernel (tile 13): units = (clip, plane, 16-column chunk); one wave per SIMD, so the block
-        # count that fills the chip once (256) and its multiples are the candidates worth timing
-        if ((g.kd, g.kh, g.kw, g.sd, g.sh, g.sw, g.pd, g.ph, g.pw) == (1, 3, 3, 1, 1, 1, 0, 1, 1) and (g.W % 4 == 0 or g.W <= 16) and g.H >= 2
-                and not g.act_f16):
-            units = g.N * g.D * -(-g.W // 16)
-            tiles = -(-M // 32) * -(-g.C // 32)
-            for nb in (256, 512, 768):
-                cands.append((13, max(1, min(units // 4, nb // tiles))))
-        # the stem kernel (conv3d_wgrad_stem.hip, tile 14): <= 4 input channels, stride 2 along H and W; its split is over
-        # (clip, od) units, one workgroup per (split, group of tap planes)
-        if g.C <= 4 and (g.sd, g.sh, g.sw) == (1, 2, 2) and g.K <= 128:
-            units = g.N * ((g.D + 2 * g.pd - g.kd) // g.sd + 1)
-            groups = (-(-g.kd // 2) if g.K <= 64 else g.kd) if g.kd > 1 else 1
-            oh = (g.H + 2 * g.ph - g.kh) // g.sh + 1
-            for nb in (256, 512, 1024, 2048):
-                sp = max(1, min(units * max(1, oh // 8), nb // groups, 1024))     # (the library chunks the output rows past N * OD units)
-                if sp * M * Nred * 4 <= (256 << 20):
-                    cands.append((14, sp))
-        return sorted(set(cands))
+    def pack_layout(self, which):
+        """Packed-weight layout the pass reads under the configuration in force: 0 = k-major fp32 rows (gather kernels; the weight
+        gradient reads none), else the LDS-halo layout, which also depends on the arithmetic (fp32 rows / 2 / 3 bf16 parts)."""
+        return 0 if which == 2 else H.lib.gca_conv_pack_layout(self.gp, which)
 
     # ---- one-off launch tuning ------------------------------------------------------------
-    def _igemm_candidates(self, M, Ntot, kred):
-        """(tile code, split) pairs: tile code = rows (32..160) | TUNE_VEC for the 256-column float4 variant."""
-        nk = -(-kred // 16)
+    def tune_key(self, which):
+        """Tune-cache key of pass `which`: library version, arithmetic ('' f32, 'b' bf16x3, 'c' bf16x6, 'h' fp16 storage), pass, geometry."""
         g = self.g
-        pointwise = g.kh == 1 and g.kw == 1 and g.sh == 1 and g.sw == 1 and g.ph == 0 and g.pw == 0
-        cands = []
-        for vec in ((0, TUNE_VEC) if pointwise else (0,)):
-            bn = 256 if vec else 128
-            for bm in (32, 64, 96, 128, 160):
-                padded = -(-M // bm) * bm
-                if padded > 1.35 * max(M, 32) and bm > 32:       # skip tile heights that mostly multiply zeros
-                    continue
-                tiles = -(-M // bm) * -(-Ntot // bn)
-                for s in (1, 2, 3, 4, 6, 8, 12, 16):
-                    if s > 1 and (tiles >= 1024 or nk // s < 4 or s * M * Ntot * 4 > (96 << 20)):
-                        continue
-                    cands.append((bm | vec, s))
-        return cands
+        geom = (g.N, g.C, g.D, g.H, g.W, g.K, g.kd, g.kh, g.kw, g.sd, g.sh, g.sw, g.pd, g.ph, g.pw, g.x_batch_stride)
+        return 'v%d%s:%d:%s' % (H.lib.gca_version(), 'h' if g.act_f16 else ('', 'b', 'c')[H.lib.gca_get_conv_math()], which,
+                                ','.join(str(int(v)) for v in geom))
 
-    def _halo_candidates(self, which, M):
-        """LDS-halo kernel candidates (tile code | TUNE_HALO, split, box code): the few boxes with the least padding of the
-        output grid x halo size, each with the tile heights that pad M least.  Unit-stride dgrad and forward only."""
-        g = self.g
-        if which == 0:
-            q, m, C = (self.out_shape[2], self.out_shape[3], self.out_shape[4]), (g.sd, g.sh, g.sw), g.C
-        else:
-            if (g.sd, g.sh, g.sw) != (1, 1, 1):
-                return []
-            q, m, C = (g.D, g.H, g.W), (1, 1, 1), g.K
-        k = (g.kd, g.kh, g.kw)
-        if C < 16 or self.taps > 64:
-            return []
-        out = []
-        for bn, nbox in ((128, 3), (256, 2)):
-            boxes = []
-            d = 1
-            while d <= bn:
-                h = 1
-                while d * h <= bn:
-                    w = bn // (d * h)
-                    b = (d, h, w)
-                    if all(b[i] <= 2 * q[i] for i in range(3)):
-                        P = 1
-                        for i in range(3):
-                            P *= (b[i] - 1) * m[i] + k[i]
-                        if P <= 384:
-                            cover = 1.0
-                            for i in range(3):
-                                cover *= -(-q[i] // b[i]) * b[i] / q[i]
-                            cost = cover * (1.0 + 0.08 * P / bn) * (1.0 if w >= 8 else (1.1 if w >= 4 else 1.3))
-                            boxes.append((cost, b))
-                    h *= 2
-                d *= 2
-            boxes.sort()
-            tmax = 5 if bn == 128 else 3
-            pads = sorted((-(-M // (32 * t)) * 32 * t, -t) for t in range(1, tmax + 1))
-            rows = [32 * -t for _, t in pads[:2]]
-            for cost, b in boxes[:nbox]:
-                if cost > 2.0:
-                    continue
-                for bm in rows:
-                    out.append((bm | TUNE_HALO, 1, b[0] | (b[1] << 8) | (b[2] << 16)))
-        return out
+    def set_code(self, which, code):
+        """Pin launch code `code` (tune.ConvCode / tune.WgradCode) for pass `which`."""
+        for field, v in zip(code._fields, code):
+            setattr(self.g, 'tune_%s_%s' % (tune.PASSES[which], field), v)
+        self.refresh()
 
     def tune(self, which, run, repack=None):
         """Measure the candidate launch configurations of pass `which` (0 fwd, 1 dgrad, 2 wgrad) with `run`
@@ -332,125 +239,68 @@ class ConvPlan:
         without it only configurations of the current layout are measured."""
         if self.tuned[which] or torch.cuda.is_current_stream_capturing():
             return
-        self.tuned[which] = True
-        g = self.g
-        N, K, OD, OH, OW = self.out_shape
-        key = '%d:%s' % (which, ','.join(str(int(v)) for v in (g.N, g.C, g.D, g.H, g.W, g.K, g.kd, g.kh, g.kw, g.sd, g.sh,
-                                                                 g.sw, g.pd, g.ph, g.pw, g.x_batch_stride)))
-        key = 'v%d%s:%s' % (H.lib.gca_version(), 'h' if g.act_f16 else ('', 'b', 'c')[H.lib.gca_get_conv_math()], key)
-        hit = _TUNE_CACHE.get(key)
 
-        def apply(c):
-            # igemm: (tile code, splits, tail code, math code, box code); wgrad: (tile shape, splits, math code); short = zeros
-            if which < 2:
-                pass_ = ('fwd', 'dgrad')[which]
-                for field, v in zip(('bm', 'splits', 'tail', 'math', 'box'), tuple(c) + (0,) * (5 - len(c))):
-                    setattr(g, 'tune_%s_%s' % (pass_, field), v)
-            else:
-                g.tune_wgrad_tile, g.tune_wgrad_splits = c[0], c[1]
-                g.tune_wgrad_math = c[2] if len(c) > 2 else 0
-            self.refresh()
-
-        def layout():
-            """Packed-weight layout the pass reads under the configuration in force: 0 = k-major fp32 rows (gather
-            kernels), else the LDS-halo layout, which also depends on the arithmetic (fp32 rows / 2 / 3 bf16 parts)."""
-            return 0 if which == 2 else H.lib.gca_conv_pack_layout(self.gp, which)
-
-        layout0 = layout()
-        if hit is not None:
-            apply(hit)
-            if H.lib.gca_conv_fwd_stat_parts(self.gp) >= 0:
-                if layout() == layout0:
-                    return                                         # still a valid launch code for this library
-                if repack is not None:
-                    repack()
-                    return
-                # The measured configuration reads another packed layout and this caller cannot re-pack (no raw weights:
-                # the plain HipConv3d.forward path).  Run on the heuristic shape of the layout at hand and leave BOTH the
-                # cache entry and the plan's "untuned" state alone: the next caller that can re-pack adopts the entry.
-                apply((0, 0, 0, 0, 0) if which < 2 else (0, 0, 0))
-                self.tuned[which] = False
-                return
-            apply((0, 0, 0, 0, 0) if which < 2 else (0, 0, 0))
-        if which == 0:
-            cands = [c + (0,) for c in self._igemm_candidates(K, N * OD * OH * OW, g.C * self.taps)]
-            cands += self._halo_candidates(0, K)
-            if g.C <= 4 and g.sw == 2 and g.kw <= 8:
-                cands.append((TUNE_STEM | 64, 1, 0))              # stem kernel (conv3d_stem.hip), box by its own heuristic
-            if g.act_f16 and self.taps == 1:
-                cands.append((TUNE_PW | 128, 1, 0))               # pointwise fp16 GEMM kernel (conv3d_pw.hip)
-        elif which == 1:
-            cands = [c + (0,) for c in self._igemm_candidates(g.C, g.N * g.D * g.H * g.W, K * self.taps)]
-            cands += self._halo_candidates(1, g.C)
-            if g.act_f16 and self.taps == 1:
-                cands.append((TUNE_PW | 128, 1, 0))
-        else:
-            cands = self._wgrad_candidates(K, g.C * self.taps, -(-(N * OD * OH * OW) // 32))
-        # The arithmetic mode is a floor on accuracy: a pass may run a MORE accurate kernel when that one is faster
-        # (tune_*_math = 1 + arithmetic; f32 > bf16x6 > bf16x3).  0 = the mode itself.
-        maths = (0,) if g.act_f16 else {0: (0,), 2: (0, 1), 1: (0, 3, 1)}[H.lib.gca_get_conv_math()]
-
-        packed_as = [layout0]
-
-        def measure(c):
-            apply(c)
-            if which == 2 and self.cfg(2)[3] & 255 != c[0]:      # shape not available for this tap count
-                return None
-            if which < 2:
-                if self.kernel(which) != _tune_kernel(c[0]):
-                    return None                                   # halo / stem kernel asked for but not runnable here (or vice versa)
-                if layout() != packed_as[0]:
-                    if repack is None:
-                        return None
-                    repack()
-                    packed_as[0] = layout()
+        def measure():
             try:
                 return _time_ms(run)
             except RuntimeError:
                 return None
+        self.search(which, measure, repack)
 
+    def _adopt(self, which, code, repack):
+        """Pin the launch code of a tune-cache hit, if the packed weights at hand allow it; -> what happened."""
+        layout = self.pack_layout(which)
+        self.set_code(which, code)
+        if H.lib.gca_conv_fwd_stat_parts(self.gp) < 0:
+            return 'stale'                                     # not a valid launch code for this library (any more)
+        if self.pack_layout(which) == layout:
+            return 'as is'
+        if repack is not None:
+            repack()
+            return 'repacked'
+        # The measured configuration reads another packed layout and this caller cannot re-pack (no raw weights: the plain
+        # HipConv3d.forward path).  It runs on the heuristic shape of the layout at hand, and BOTH the cache entry and the
+        # plan's "untuned" state are left alone: the next caller that can re-pack adopts the entry.
+        return 'cannot repack'
+
+    def search(self, which, measure, repack=None):
+        """tune() behind its device: `measure()` times the pass under the configuration in force (None = cannot run)."""
+        self.tuned[which] = True
+        key, heuristic = self.tune_key(which), tune.CODES[which]()
+        packed_as = self.pack_layout(which)
+        hit = _TUNE_CACHE.get(key)
+        if hit is not None:
+            adopted = self._adopt(which, tune.CODES[which](*hit), repack)
+            if adopted in ('stale', 'cannot repack'):
+                self.set_code(which, heuristic)
+            self.tuned[which] = adopted != 'cannot repack'
+            if adopted != 'stale':
+                return
+        g, math = self.g, H.lib.gca_get_conv_math()
         timed = []
-        for m in maths:
-            for c in cands:
-                c = (c[0], c[1], 0, m, c[2]) if which < 2 else (c[0], c[1], m)
-                t = measure(c)
-                if t is not None:
-                    timed.append((t, c))
-        timed.sort()
-        if which < 2 and timed and not g.act_f16:          # (two-phase launches are built for fp32 storage only)
-            # two-phase launches on the fastest single-launch shapes: tall tiles for the full waves of workgroups, short
-            # tiles for the remainder (how many workgroups run at once is not known here, so a few guesses are measured)
-            M, Ntot = (K, N * OD * OH * OW) if which == 0 else (g.C, g.N * g.D * g.H * g.W)
-            single_class = which == 0 or (g.sd == 1 and g.sh == 1 and g.sw == 1)
-            tilesN = -(-Ntot // 128)
-            for _, base in list(timed[:2]):
-                bm, sp, m = base[0], base[1], base[3]
-                if not single_class or sp != 1 or bm >= TUNE_VEC or bm <= 32:
+        for round_ in (1, 2):               # every candidate, then two-phase forms of the two fastest
+            codes = tune.candidates(which, g, math) if round_ == 1 else [c for _, base in sorted(timed)[:2]
+                                                                          for c in tune.two_phase(which, g, base)]
+            for code in codes:
+                self.set_code(which, code)
+                # where the library cannot run what a code asks for (tile shape not built for this tap count, halo / stem
+                # kernel not runnable here) it falls back to another kernel: nothing new to measure
+                asked = self.cfg(2)[3] & 255 == code.tile if which == 2 else self.kernel(which) == _tune_kernel(code.bm)
+                if not asked:
                     continue
-                tilesM = -(-M // bm)
-                seen = set()
-                for slots in (512, 768, 1024, 1280):
-                    full = (tilesM * tilesN // slots) * slots
-                    main_cols = full // tilesM
-                    if main_cols <= 0 or main_cols >= tilesN or main_cols in seen:
+                if self.pack_layout(which) != packed_as:
+                    if repack is None:
                         continue
-                    seen.add(main_cols)
-                    for tail_rows in (32, 64):
-                        if tail_rows >= bm:
-                            continue
-                        c = (bm, 1, (tail_rows // 32) | (main_cols << 8), m, 0)
-                        t = measure(c)
-                        if t is not None:
-                            timed.append((t, c))
-            timed.sort()
-        best = timed[0][1] if timed else None
-        if best is not None:
-            _TUNE_CACHE[key] = tuple(int(v) for v in best)
+                    repack()
+                    packed_as = self.pack_layout(which)
+                t = measure()
+                if t is not None:
+                    timed.append((t, code))
+        if timed:
+            _TUNE_CACHE[key] = tuple(min(timed)[1])
             _TUNE_DIRTY[0] = True
-            apply(best)
-        else:
-            apply((0, 0, 0, 0, 0) if which < 2 else (0, 0, 0))
-        if which < 2 and repack is not None and layout() != packed_as[0]:
+        self.set_code(which, min(timed)[1] if timed else heuristic)
+        if repack is not None and self.pack_layout(which) != packed_as:
             repack()
 
 
@@ -493,16 +343,18 @@ def _repacker(plan, which, w_raw, wpack):
     return lambda: H.call('gca_conv_pack', plan.gp, which, ptr(w_raw), ptr(wpack), stream())
 
 
+def _stat_pair(plan, device):
+    """Uninitialised (sum, sum of squares) BatchNorm partials of a forward under the launch shape in force: [K][plan.parts] each."""
+    return tuple(torch.empty((plan.g.K, plan.parts), dtype=F32, device=device) for _ in range(2))
+
+
 def conv_fwd(plan, x, wpack, bias=None, stats=False, w_raw=None):
     """-> y [, (stat_sum, stat_sq)]  with stat layout [K][plan.parts].  w_raw: the unpacked weights behind `wpack`; lets
     the one-off launch tuning try configurations that read another packed layout (it re-packs into `wpack`)."""
     y = torch.empty(plan.out_shape, dtype=plan.act_dtype, device=x.device)
     if not plan.tuned[0]:
         plan.tune(0, lambda: _conv_fwd_launch(plan, x, wpack, bias, y, None, None), _repacker(plan, 0, w_raw, wpack))
-    ss = sq = None
-    if stats:
-        ss = torch.empty((plan.g.K, plan.parts), dtype=F32, device=x.device)
-        sq = torch.empty((plan.g.K, plan.parts), dtype=F32, device=x.device)
+    ss, sq = _stat_pair(plan, x.device) if stats else (None, None)
     _conv_fwd_launch(plan, x, wpack, bias, y, ss, sq)
     return (y, (ss, sq)) if stats else y
 
@@ -516,10 +368,7 @@ def conv_xf_ok(plan):
 def conv_fwd_xf(plan, y_in, scale, shift, wpack, stats=False):
     """conv_fwd on z = relu(y_in * scale[c] + shift[c]) without materialising z (scale / shift: padded rows of bn_finalize)."""
     y = torch.empty(plan.out_shape, dtype=F32, device=y_in.device)
-    ss = sq = None
-    if stats:
-        ss = torch.empty((plan.g.K, plan.parts), dtype=F32, device=y_in.device)
-        sq = torch.empty((plan.g.K, plan.parts), dtype=F32, device=y_in.device)
+    ss, sq = _stat_pair(plan, y_in.device) if stats else (None, None)
     ws = WS.get(plan.fwd_ws, y_in.device) if plan.fwd_ws else None
     H.call('gca_conv_fwd_xf', plan.gp, ptr(y_in), ptr(scale), ptr(shift), ptr(wpack), ptr(plan.table(0)), None, ptr(y), ptr(ss),
            ptr(sq), ptr(ws), stream())
