@@ -388,6 +388,34 @@ int gca_clip_prepare(const uint8_t* frames, int64_t b, int64_t views, int64_t T,
                      const int32_t* params, const float* mean255, const float* inv_std255, int64_t H, int64_t W,
                      void* out, int out_f16, void* stream);
 
+/* The whole contrastive chain on the device (opt-in; gca_clip_prepare is unchanged): VideoRandomResizedCrop -> colour jitter
+ * -> grayscale -> Gaussian blur -> flip -> normalise -> to-tensor (lib/data/transform/build.py:45-62,
+ * consistency_transforms.py:81-145, 226-340) from decoded uint8 source frames and one parameter record per (clip, view).
+ * The arithmetic is the one written down in tests/augment_ref.py (integer / fixed point, or fp32 with one rounding per
+ * operation, no contraction), which the kernels reproduce bit for bit.  cv2 / albumentations are not available to compare
+ * with: parity with cv2's own rounding is UNVERIFIED and not claimed.
+ *   frames       : (b, views, T, Hs, Ws, 3) uint8, device
+ *   records      : (b, views, 24) int32, device; records_host: the same words in HOST memory (they are validated there)
+ *                  0 y0  1 x0  2 ch  3 cw   crop box inside the source frame (it may be smaller than the output: upscaling)
+ *                  4 flip  5 gray  6 k      blur size, 0 (off) | 3 | 5 | 7, radius < min(H, W)
+ *                  7..10 perm               order of the jitter ops: 0 brightness, 1 contrast, 2 saturation, 3 hue
+ *                  11 mask                  bit op set = op applied (0 = no jitter; factor 1 / hue 0 = identity = bit clear)
+ *                  12 f_c  13 1 - f_c  14 f_s  15 1 - f_s   contrast / saturation factors, fp32 bit patterns
+ *                  16..22 blur taps         k 12-bit fixed-point weights >= 0 that sum to 4096, the rest 0;   23: 0
+ *   taps         : (b, views, H + W, 4) int16, device, 8-byte aligned: per output row (first H) / column (last W)
+ *                  {i0, i1, c0, c1}: two source indices in frame coordinates and their 11-bit weights, c0 + c1 = 2048
+ *   luts         : (b, views, 2, 256) uint8, device: brightness table; hue table (H in [0, 180) -> shifted H)
+ *   divtab       : (2, 256) int32, device: round((255 << 12) / i) and round((180 << 12) / (6 i)), entry 0 = 0
+ *   mean255, inv_std255, out, out_f16 : as gca_clip_prepare
+ *   ws           : gca_clip_augment_ws_bytes(b, views, T) bytes, device: one integer gray sum per frame (contrast)
+ * GCA_EINVAL for a crop box outside the frame, k outside {0, 3, 5, 7} or too wide for the output, a perm that is no
+ * permutation, blur taps that do not sum to 4096.  At most two launches (the reduction for contrast, the main pass). */
+int64_t gca_clip_augment_ws_bytes(int64_t b, int64_t views, int64_t T);
+int gca_clip_augment(const uint8_t* frames, int64_t b, int64_t views, int64_t T, int64_t Hs, int64_t Ws,
+                     const int32_t* records_host, const int32_t* records, const int16_t* taps, const uint8_t* luts,
+                     const int32_t* divtab, const float* mean255, const float* inv_std255, int64_t H, int64_t W,
+                     void* out, int out_f16, void* ws, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Multi-tensor parameter updates over flat, 256-element-aligned parameter arenas.
  * _momentum_update (tools/train_video_contrast_dis.py:177-180) and torch.optim.SGD as

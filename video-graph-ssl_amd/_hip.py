@@ -114,6 +114,9 @@ SIGNATURES = {
     'gca_reduce_jobs_finalize_host': (c_i64, [c_vp, c_i64]),
     'gca_splitk_reduce_batched': (c_i32, [c_vp, c_i64, c_i64, c_vp]),
     'gca_clip_prepare': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_vp]),
+    'gca_clip_augment_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
+    'gca_clip_augment': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                 c_vp, c_i32, c_vp, c_vp]),
     'gca_rank_ge': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     'gca_grad_unscale_clip': (c_i32, [c_vp, c_i64, c_f32, c_vp, c_f32, c_f32, c_i32, c_f32, c_vp, c_vp, c_vp]),
     'gca_scale_dev': (c_i32, [c_vp, c_i64, c_vp, c_f32, c_vp]),
