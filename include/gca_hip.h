@@ -189,6 +189,21 @@ int gca_conv_fwd_xf(const gca_conv_geom* g, const void* x, const float* in_scale
                     const int32_t* table, const float* bias, void* y, float* stat_sum, float* stat_sq, void* ws, void* stream);
 int gca_conv_wgrad_xf(const gca_conv_geom* g, const void* x, const float* in_scale, const float* in_shift, const void* dy,
                       const int32_t* table, float* dw, int accumulate, void* ws, void* stream);
+/* BatchNorm BACKWARD of the conv's own BatchNorm applied where the weight gradient reads dy.  A first-layer conv has no dgrad
+ * (resnet2p1d.py:162-168, s3d_1.py:35, resnet.py:120-126: the clip needs no gradient), so the dy that gca_bn_bwd writes has one
+ * reader, this weight gradient: a full write and a full read of the largest tensor of the model.  gca_bn_bwd_sums (BatchNorm
+ * section) leaves the per-channel constants instead; gca_conv_wgrad_dzf / _partial take dz (gradient behind BatchNorm + ReLU,
+ * dense), the conv output y and those constants where gca_conv_wgrad / gca_conv_wgrad_partial take dy, and form
+ * dy = A * (m * dz - B - (y - mean) * invstd * Cc) per element in registers, operation for operation what gca_bn_bwd stores.
+ * relu: 0 or 2, as given to gca_bn_bwd_sums.  gca_conv_dzf_ok(g) = 1 when, under the tune_* fields in force, the weight
+ * gradient of g runs on the stem kernel (tune_wgrad_tile 14 on a geometry it takes); otherwise these entries return GCA_EINVAL
+ * and the caller runs gca_bn_bwd + gca_conv_wgrad.  `table` is not read (may be NULL).  Same slabs, splits and workspace as
+ * gca_conv_wgrad. */
+int gca_conv_dzf_ok(const gca_conv_geom* g);
+int gca_conv_wgrad_dzf(const gca_conv_geom* g, const void* x, const void* dz, const void* y, const float* consts, int relu,
+                       const int32_t* table, float* dw, int accumulate, void* ws, void* stream);
+int gca_conv_wgrad_dzf_partial(const gca_conv_geom* g, const void* x, const void* dz, const void* y, const float* consts, int relu,
+                               const int32_t* table, void* slabs, int32_t* out_splits, void* stream);
 int64_t gca_reduce_jobs_finalize_host(gca_reduce_job* jobs, int64_t njobs);
 int gca_splitk_reduce_batched(const gca_reduce_job* jobs_dev, int64_t njobs, int64_t total_blocks, void* stream);
 /* Launch shape the wgrad kernel will use for g: out4 = {tile rows (output channels), tile columns (C*taps),
@@ -255,6 +270,15 @@ int gca_bn_bwd(const void* dz_in, const void* z, const void* x, const float* gam
                int64_t N, int64_t C, int64_t SP, void* dx, float* dgamma, float* dbeta,
                void* dres, int dres_accumulate, int64_t z_batch_stride /* of dz_in and z */,
                const float* scale, const float* shift, void* ws, int act_f16, void* stream);
+/* gca_bn_bwd without its apply pass, for a consumer that forms dx itself (gca_conv_wgrad_dzf): the same reduce and finalize
+ * launches at every size, so dgamma / dbeta (+=) get the bits gca_bn_bwd gives them above the one-workgroup regime
+ * (N*SP > 32768).  relu: 0 or 2.  consts: gca_bn_bwd_consts_elems(C) floats = 7 rows of stride Cp = 16*ceil(C/16) + 16
+ * (the padding of the _xf scale / shift rows): A = gamma*invstd, B = sum(m*dz)/M, Cc = sum(m*dz*xhat)/M, mean, invstd, and
+ * the forward's scale, shift (zeros when relu = 0); the pad c >= C of every row is zero.  ws: gca_bn_bwd_ws_bytes(). */
+int64_t gca_bn_bwd_consts_elems(int64_t C);
+int gca_bn_bwd_sums(const void* dz_in, const void* x, const float* gamma, const float* save_mean, const float* save_invstd,
+                    int relu, int64_t N, int64_t C, int64_t SP, float* dgamma, float* dbeta, int64_t z_batch_stride /* of dz_in */,
+                    const float* scale, const float* shift, float* consts, void* ws, int act_f16, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Pooling.  MaxPool3d: resnet2p1d.py:178, s3d_1.py:10,13,16,22,87, temporal_graph.py:100

@@ -226,6 +226,22 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
   }
 }
 
+// gca_bn_bwd_sums: rows 3..6 of the constant array [BN_BWD_CONST_ROWS][Cp] -- what bn_bwd_apply_kernel reads per channel beside the
+// coefficient triplet (rows 0..2, written by bn_bwd_finalize_kernel with Cp as its row stride) -- and zeros in the pad c >= C
+// of every row: a consumer's lane on a row past C computes A * (0 - B - (0 - mean) * invstd * Cc) = 0
+__global__ __launch_bounds__(256) void bn_bwd_consts_kernel(
+    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ scale,
+    const float* __restrict__ shift, int relu, int C, int Cp, float* __restrict__ consts) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= Cp) return;
+  const bool live = c < C;
+  consts[3 * Cp + c] = live ? mean[c] : 0.f;
+  consts[4 * Cp + c] = live ? invstd[c] : 0.f;
+  consts[5 * Cp + c] = live && relu == 2 ? scale[c] : 0.f;
+  consts[6 * Cp + c] = live && relu == 2 ? shift[c] : 0.f;
+  if (!live) { consts[c] = 0.f; consts[Cp + c] = 0.f; consts[2 * Cp + c] = 0.f; }
+}
+
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const T* __restrict__ dzin, const T* __restrict__ z, const T* __restrict__ x,
@@ -630,6 +646,26 @@ static int bn_train_fwd_t(const float* stat_sum, const float* stat_sq, int64_t P
   return bn_apply_t<T>(x, scale, shift, residual, relu, N, C, SP, z, z_batch_stride, stream);
 }
 
+// The two sum launches of the backward pass above the one-workgroup regime: per-part (sum dz, sum dz * xhat), then per channel
+// the fp64 fold, dgamma / dbeta (+=) and the coefficient triplet coef[0 | cstride | 2 cstride + c] = (gamma * invstd, S1 / M, S2 / M).
+template <typename T>
+static void bn_bwd_sums_launch(const T* dz_in, const T* z, const T* x, const float* gamma, const float* save_mean,
+                               const float* save_invstd, int relu, int64_t N, int64_t C, int64_t SP, long long zs, float* dgamma,
+                               float* dbeta, const float* scale, const float* shift, void* ws, float* coef, long long cstride,
+                               hipStream_t st) {
+  const int P = (int)stats_parts(N, C, SP);
+  float* p0 = reinterpret_cast<float*>(ws);
+  float* p1 = p0 + (long long)C * P;
+  if ((SP % 4 == 0) && (zs % 4 == 0) && (((uintptr_t)dz_in | (uintptr_t)z | (uintptr_t)x) % 16 == 0))
+    hipLaunchKernelGGL((bn_reduce_kernel<T, 1, 4>), dim3(P, (unsigned)C), dim3(256), 0, st, dz_in, z, x, save_mean,
+                       save_invstd, relu, (long long)N, (long long)C, (long long)SP, zs, P, p0, p1, scale, shift);
+  else
+    hipLaunchKernelGGL((bn_reduce_kernel<T, 1, 1>), dim3(P, (unsigned)C), dim3(256), 0, st, dz_in, z, x, save_mean,
+                       save_invstd, relu, (long long)N, (long long)C, (long long)SP, zs, P, p0, p1, scale, shift);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)C), dim3(256), 0, st, p0, p1, P, (double)N * (double)SP,
+                     gamma, save_invstd, dgamma, dbeta, coef, cstride);
+}
+
 template <typename T>
 static int bn_bwd_t(const T* dz_in, const T* z, const T* x, const float* gamma,
                const float* save_mean, const float* save_invstd, int relu,
@@ -653,18 +689,9 @@ static int bn_bwd_t(const T* dz_in, const T* z, const T* x, const float* gamma,
                          relu, (int)N, (int)C, (int)SP, zs, dx, dgamma, dbeta, dres, dres_accumulate, scale, shift);
     return gca_launch_status();
   }
-  const int P = (int)stats_parts(N, C, SP);
-  float* p0 = reinterpret_cast<float*>(ws);
-  float* p1 = p0 + (long long)C * P;
-  float* coef = p1 + (long long)C * P;
-  if ((SP % 4 == 0) && (zs % 4 == 0) && (((uintptr_t)dz_in | (uintptr_t)z | (uintptr_t)x) % 16 == 0))
-    hipLaunchKernelGGL((bn_reduce_kernel<T, 1, 4>), dim3(P, (unsigned)C), dim3(256), 0, st, dz_in, z, x, save_mean,
-                       save_invstd, relu, (long long)N, (long long)C, (long long)SP, zs, P, p0, p1, scale, shift);
-  else
-    hipLaunchKernelGGL((bn_reduce_kernel<T, 1, 1>), dim3(P, (unsigned)C), dim3(256), 0, st, dz_in, z, x, save_mean,
-                       save_invstd, relu, (long long)N, (long long)C, (long long)SP, zs, P, p0, p1, scale, shift);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)C), dim3(256), 0, st, p0, p1, P, (double)N * (double)SP,
-                     gamma, save_invstd, dgamma, dbeta, coef, (long long)C);
+  float* coef = reinterpret_cast<float*>(ws) + 2 * (long long)C * stats_parts(N, C, SP);
+  bn_bwd_sums_launch<T>(dz_in, z, x, gamma, save_mean, save_invstd, relu, N, C, SP, zs, dgamma, dbeta, scale, shift, ws, coef,
+                        (long long)C, st);
   const long long total = (long long)N * C * SP;
   const bool v4 = (SP % 4 == 0) && (zs % 4 == 0) &&
                   (((uintptr_t)dz_in | (uintptr_t)z | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)dres) % 16 == 0);
@@ -674,6 +701,26 @@ static int bn_bwd_t(const T* dz_in, const T* z, const T* x, const float* gamma,
   else
     hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 1>), dim3(ew_grid(total, 1)), dim3(256), 0, st, dz_in, z, x, save_mean,
                        save_invstd, coef, relu, total, (long long)C, (long long)SP, zs, dx, dres, dres_accumulate, scale, shift);
+  return gca_launch_status();
+}
+
+// gca_bn_bwd without its apply pass: the same two sum launches (same dgamma / dbeta bits) at EVERY size, and the constants of
+// the apply pass left in `consts` for the kernel that forms dx where it consumes it (gca_conv_wgrad_dzf)
+template <typename T>
+static int bn_bwd_sums_t(const T* dz_in, const T* x, const float* gamma, const float* save_mean, const float* save_invstd,
+                         int relu, int64_t N, int64_t C, int64_t SP, float* dgamma, float* dbeta, int64_t z_batch_stride,
+                         const float* scale, const float* shift, float* consts, void* ws, void* stream) {
+  if (!dz_in || !x || !save_mean || !save_invstd || !consts || !ws || N <= 0 || C <= 0 || SP <= 0) return GCA_EINVAL;
+  if ((relu != 0 && relu != 2) || (relu == 2 && (!scale || !shift))) return GCA_EINVAL;      // (mode 1 reads z: not a per-lane constant)
+  if (z_batch_stride != 0 && z_batch_stride < C * SP) return GCA_EINVAL;
+  if (C > 0x7fffffffLL - 32) return GCA_EINVAL;
+  const long long zs = z_batch_stride ? z_batch_stride : C * SP;
+  const int Cp = (int)gca_bn_consts_stride(C);
+  hipStream_t st = (hipStream_t)stream;
+  bn_bwd_sums_launch<T>(dz_in, dz_in, x, gamma, save_mean, save_invstd, relu, N, C, SP, zs, dgamma, dbeta, scale, shift, ws,
+                        consts, (long long)Cp, st);
+  hipLaunchKernelGGL(bn_bwd_consts_kernel, dim3((unsigned)gca_ceil_div(Cp, 256)), dim3(256), 0, st, save_mean, save_invstd,
+                     scale, shift, relu, (int)C, Cp, consts);
   return gca_launch_status();
 }
 
@@ -764,6 +811,21 @@ int gca_bn_bwd(const void* dz_in, const void* z, const void* x, const float* gam
                               scale, shift, ws, stream);
   return bn_bwd_t<float>((const float*)dz_in, (const float*)z, (const float*)x, gamma, save_mean, save_invstd, relu, N, C, SP,
                          (float*)dx, dgamma, dbeta, (float*)dres, dres_accumulate, z_batch_stride, scale, shift, ws, stream);
+}
+
+int64_t gca_bn_bwd_consts_elems(int64_t C) {
+  if (C <= 0 || C > 0x7fffffffLL - 32) return GCA_EINVAL;
+  return GCA_BN_BWD_CONST_ROWS * gca_bn_consts_stride(C);
+}
+
+int gca_bn_bwd_sums(const void* dz_in, const void* x, const float* gamma, const float* save_mean, const float* save_invstd,
+                    int relu, int64_t N, int64_t C, int64_t SP, float* dgamma, float* dbeta, int64_t z_batch_stride,
+                    const float* scale, const float* shift, float* consts, void* ws, int act_f16, void* stream) {
+  if (act_f16)
+    return bn_bwd_sums_t<gca_half>((const gca_half*)dz_in, (const gca_half*)x, gamma, save_mean, save_invstd, relu, N, C, SP,
+                                   dgamma, dbeta, z_batch_stride, scale, shift, consts, ws, stream);
+  return bn_bwd_sums_t<float>((const float*)dz_in, (const float*)x, gamma, save_mean, save_invstd, relu, N, C, SP, dgamma, dbeta,
+                              z_batch_stride, scale, shift, consts, ws, stream);
 }
 
 }  // extern "C"

@@ -455,9 +455,9 @@ extern "C" int gca_conv_halo_occupancy(int tm, int tn, int math, int64_t lds_byt
   int n = -1;
 #define GCA_HO(A, B, M)                                                                                                   \
   if (tm == A && tn == B && math == M) {                                                                                  \
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<A, B, M>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                        160 << 10);                                                                                       \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_halo_kernel<A, B, M>, 256, (size_t)lds_bytes) != hipSuccess) \
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<A, B, M>),                                    \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10) != hipSuccess ||                       \
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_halo_kernel<A, B, M>, 256, (size_t)lds_bytes) != hipSuccess) \
       n = -1;                                                                                                             \
   }
   GCA_HO(2, 2, 2) GCA_HO(2, 2, 0) GCA_HO(5, 1, 2) GCA_HO(4, 1, 2) GCA_HO(3, 1, 2) GCA_HO(2, 1, 2) GCA_HO(1, 1, 2)

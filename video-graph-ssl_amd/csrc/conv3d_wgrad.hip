@@ -782,6 +782,29 @@ static int wgrad_partial_launch(const gca_conv_geom* g, const void* x_, const vo
   return rc ? rc : L.splits;
 }
 
+// the stem kernel on (dz, y, constants of gca_bn_bwd_sums) instead of dy; -> splits (> 0) or a negative status
+static int wgrad_dzf_launch(const gca_conv_geom* g, const void* x, const void* dz, const void* y, const float* consts, int relu,
+                            void* ws, hipStream_t st) {
+  if (!geom_ok(g) || !x || !dz || !y || !consts || !ws || (relu != 0 && relu != 2)) return GCA_EINVAL;
+  WgradLaunch L = resolve_wgrad(g);
+  if (!wgrad_stem_dzf_plan(g, L) || L.blocks > 0x7fffffffLL) return GCA_EINVAL;
+  if ((uintptr_t)x % L.x_align || (uintptr_t)dz % L.dy_align || (uintptr_t)y % L.dy_align || (uintptr_t)consts % 4) return GCA_EINVAL;
+  const int rc = wgrad_stem_dzf_run(L, x, dz, y, consts, relu, reinterpret_cast<float*>(ws), st);
+  return rc ? rc : L.splits;
+}
+
+// dw (+)= sum of the `splits` slabs, in the fixed order
+static int wgrad_reduce_launch(const gca_conv_geom* g, float* slab, float* dw, int splits, int accumulate, hipStream_t st) {
+  const long long n = (long long)g->K * g->C * taps(g);
+  if (n % 4 == 0 && ((uintptr_t)slab % 16) == 0 && ((uintptr_t)dw % 16) == 0)
+    hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)gca_ceil_div(n / 4, 64)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(slab), reinterpret_cast<float4*>(dw), n / 4, splits, accumulate ? 1 : 0);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)gca_ceil_div(n, 64)), dim3(256), 0, st, slab, dw, n,
+                       splits, accumulate ? 1 : 0);
+  return gca_launch_status();
+}
+
 int gca_conv_wgrad(const gca_conv_geom* g, const void* x_, const void* dy_, const int32_t* table,
                    float* dw, int accumulate, void* ws, void* stream) {
   return gca_conv_wgrad_xf(g, x_, nullptr, nullptr, dy_, table, dw, accumulate, ws, stream);
@@ -793,15 +816,33 @@ int gca_conv_wgrad_xf(const gca_conv_geom* g, const void* x_, const float* in_sc
   hipStream_t st = (hipStream_t)stream;
   const int splits = wgrad_partial_launch(g, x_, dy_, table, ws, st, in_scale, in_shift);
   if (splits < 0) return splits;
-  float* slab = reinterpret_cast<float*>(ws);
-  const long long n = (long long)g->K * g->C * taps(g);
-  if (n % 4 == 0 && ((uintptr_t)slab % 16) == 0 && ((uintptr_t)dw % 16) == 0)
-    hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)gca_ceil_div(n / 4, 64)), dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(slab), reinterpret_cast<float4*>(dw), n / 4, splits, accumulate ? 1 : 0);
-  else
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)gca_ceil_div(n, 64)), dim3(256), 0, st, slab, dw, n,
-                       splits, accumulate ? 1 : 0);
-  return gca_launch_status();
+  return wgrad_reduce_launch(g, reinterpret_cast<float*>(ws), dw, splits, accumulate, st);
+}
+
+int gca_conv_dzf_ok(const gca_conv_geom* g) {
+  if (!geom_ok(g)) return 0;
+  WgradLaunch L = resolve_wgrad(g);
+  return wgrad_stem_dzf_plan(g, L) ? 1 : 0;
+}
+
+int gca_conv_wgrad_dzf(const gca_conv_geom* g, const void* x, const void* dz, const void* y, const float* consts, int relu,
+                       const int32_t* table, float* dw, int accumulate, void* ws, void* stream) {
+  (void)table;                                    // (the stem kernel reads no gather table; kept for the shape of the ABI)
+  if (!dw) return GCA_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int splits = wgrad_dzf_launch(g, x, dz, y, consts, relu, ws, st);
+  if (splits < 0) return splits;
+  return wgrad_reduce_launch(g, reinterpret_cast<float*>(ws), dw, splits, accumulate, st);
+}
+
+int gca_conv_wgrad_dzf_partial(const gca_conv_geom* g, const void* x, const void* dz, const void* y, const float* consts, int relu,
+                               const int32_t* table, void* slabs, int32_t* out_splits, void* stream) {
+  (void)table;
+  if (!out_splits) return GCA_EINVAL;
+  const int splits = wgrad_dzf_launch(g, x, dz, y, consts, relu, slabs, (hipStream_t)stream);
+  if (splits < 0) return splits;
+  *out_splits = splits;
+  return GCA_OK;
 }
 
 int gca_conv_wgrad_partial(const gca_conv_geom* g, const void* x, const float* in_scale, const float* in_shift, const void* dy,

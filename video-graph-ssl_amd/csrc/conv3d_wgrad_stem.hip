@@ -28,6 +28,14 @@
 //     tap planes in the zero padding are skipped;
 //   * one fp32 slab per workgroup "split" in dW's own layout, folded by the batched split-K reduction like every other weight
 //     gradient (fixed order: deterministic).
+//
+// DZF form (gca_conv_wgrad_dzf): the conv's BatchNorm backward never writes dY.  The kernel takes the gradient dz behind the
+// BatchNorm (+ ReLU), the conv output y and the per-channel constants of gca_bn_bwd_sums; y travels by the same LDS-DMA in the
+// same fragment order into the second half of a stage buffer, and a lane -- whose fragment row IS a channel -- forms
+// dY = A * (m * dz - B - (y - mean) * invstd * Cc), operation for operation what bn_bwd_apply_kernel stores, in registers
+// between the read-back and the bf16 split (fp16 storage: rounded to fp16 as the store would, then packed).  Positions past OW
+// and rows past K are masked after the transform (the DMA zero-fills dz AND y there, and the transform of (0, 0) is not 0).
+// A stage holds half as many steps, so dz + y take the LDS of the plain form's dY: both forms run two workgroups per CU.
 #include "conv_common.h"
 
 using namespace gca_conv;
@@ -60,9 +68,12 @@ __device__ __forceinline__ i32x4 make_rsrc(const void* base, unsigned bytes) {
   return r;
 }
 
-template <int MATH>      // 1: bf16x3 (hi, lo), 2: bf16x6 (hi, mid, lo) on fp32 tensors; 3: fp16 tensors, one f16 product
-__global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __restrict__ x, const void* __restrict__ dy,
-                                                              float* __restrict__ slab, const StwParams p) {
+// MATH 1: bf16x3 (hi, lo), 2: bf16x6 (hi, mid, lo) on fp32 tensors; 3: fp16 tensors, one f16 product.  DZF: `dy` is dz, and
+// (yv, consts, relu) describe the BatchNorm backward applied to it on the fly
+template <int MATH, bool DZF>
+__device__ __forceinline__ void stw_body(const void* __restrict__ x, const void* __restrict__ dy, const void* __restrict__ yv,
+                                         const float* __restrict__ consts, const int relu, float* __restrict__ slab,
+                                         const StwParams& p) {
   constexpr bool F16 = MATH == 3;
   constexpr int NP = MATH == 2 ? 3 : (MATH == 1 ? 2 : 1);
   constexpr unsigned ES = F16 ? 2u : 4u;
@@ -70,7 +81,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __rest
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const XZ = smem;                      // zeros: what the dead columns (>= ncols) of the last tile read
   unsigned char* const XR = smem + p.ZB;               // [g][RING][C][NP][4 arrays][ARRB]
-  unsigned char* const DYT = XR + p.g * p.PLS;         // [2][SS][nrt][NQ][1 KB]
+  unsigned char* const DYT = XR + p.g * p.PLS;         // [2][SS][nrt][NQ][1 KB]  (DZF: [2][dz | y][SS][nrt][NQ][1 KB])
+  const int BST = DZF ? 2 * p.DYB : p.DYB;             // bytes between the two stage buffers
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lh = lane >> 5, ll = lane & 31;
@@ -87,9 +99,33 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __rest
   const int kd = grp * p.g + kdl;
 
   const i32x4 rx = make_rsrc(x, p.x_bytes), ry = make_rsrc(dy, p.dy_bytes);
+  const i32x4 rz = make_rsrc(DZF ? yv : dy, p.dy_bytes);                // the conv output y (same shape as dz)
   const __amdgpu_buffer_rsrc_t bx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, p.x_bytes, 0x00020000);
   (void)rx;
   const unsigned dyt_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)(lds_void*)DYT);
+
+  // ---- DZF: BatchNorm-backward constants of this lane's channel in each of the wave's two row tiles (names as in
+  // bn_bwd_apply_kernel); a row past K reads channel 0 and is masked below
+  float bnA[2], bnB[2], bnC[2], bnMu[2], bnIs[2], bnSc[2], bnSf[2];
+  bool kok[2];
+  const bool rmask = relu == 2;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int k = (r0 + i) * 32 + ll;
+    kok[i] = k < p.K;
+    if (DZF) {
+      const int cp = (int)gca_bn_consts_stride(p.K), kc = kok[i] ? k : 0;
+      bnA[i] = consts[GCA_BN_A * cp + kc]; bnB[i] = consts[GCA_BN_B * cp + kc]; bnC[i] = consts[GCA_BN_CC * cp + kc];
+      bnMu[i] = consts[GCA_BN_MEAN * cp + kc]; bnIs[i] = consts[GCA_BN_INVSTD * cp + kc];
+      bnSc[i] = consts[GCA_BN_SCALE * cp + kc]; bnSf[i] = consts[GCA_BN_SHIFT * cp + kc];
+    }
+  }
+  // dY of one element from (dz, y): the statements of bn_bwd_apply_kernel in its order, then the range mask
+  auto bn_dy = [&](float d, const float xv, const int i, const bool live) __attribute__((always_inline)) -> float {
+    if (rmask && !(xv * bnSc[i] + bnSf[i] > 0.f)) d = 0.f;
+    const float o = bnA[i] * (d - bnB[i] - (xv - bnMu[i]) * bnIs[i] * bnC[i]);
+    return live ? o : 0.f;
+  };
 
   // ---- columns of this lane: col = ct * 32 + ll = (b * C + c) * KW + e
   unsigned cB[NB];             // LDS byte offset inside the ring without the row slot (plane, channel, array, shift)
@@ -222,7 +258,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __rest
         const int step = sg * p.SS + st;
         const unsigned v = dy_voff(rtile, q, step);
         const unsigned so = (unsigned)__builtin_amdgcn_readfirstlane((int)(rowb + (unsigned)(step * 16) * ES));
-        dma16(ry, v, so, dyt_lds + (unsigned)((it & 1) * p.DYB + pc * 1024));
+        dma16(ry, v, so, dyt_lds + (unsigned)((it & 1) * BST + pc * 1024));
+        if (DZF) dma16(rz, v, so, dyt_lds + (unsigned)((it & 1) * BST + p.DYB + pc * 1024));
       }
     };
 
@@ -251,7 +288,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __rest
       if (it + 1 < total) dy_issue(it + 1);
       if (sg == 0) x_issue(oh + 2);
       if (wave_on) {
-        const unsigned char* Ab = DYT + (it & 1) * p.DYB + lane * 16;
+        const unsigned char* Ab = DYT + (it & 1) * BST + lane * 16;
         unsigned baddr[NB];
 #pragma unroll
         for (int ct = 0; ct < NB; ++ct) baddr[ct] = dead[ct] ? 0u : (unsigned)(p.ZB + rB[ct] * p.RS) + cB[ct];
@@ -263,10 +300,29 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __rest
           uint4 af[2][NP];
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            if (F16) af[i][0] = *reinterpret_cast<const uint4*>(Ab + (st * p.nrt + r0 + i) * 1024);
-            else {
-              const float4 a0 = *reinterpret_cast<const float4*>(Ab + ((st * p.nrt + r0 + i) * 2) * 1024);
-              const float4 a1 = *reinterpret_cast<const float4*>(Ab + ((st * p.nrt + r0 + i) * 2 + 1) * 1024);
+            const bool live = kok[i] && 16 * step + 8 * lh < p.OW;       // (OW % 8 == 0: a lane's 8 positions stand or fall together)
+            if (F16) {
+              af[i][0] = *reinterpret_cast<const uint4*>(Ab + (st * p.nrt + r0 + i) * 1024);
+              if (DZF) {
+                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+                const h8 dz8 = __builtin_bit_cast(h8, af[i][0]);
+                const h8 y8 = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(Ab + p.DYB + (st * p.nrt + r0 + i) * 1024));
+                h8 o8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o8[e] = (_Float16)bn_dy((float)dz8[e], (float)y8[e], i, live);
+                af[i][0] = __builtin_bit_cast(uint4, o8);
+              }
+            } else {
+              float4 a0 = *reinterpret_cast<const float4*>(Ab + ((st * p.nrt + r0 + i) * 2) * 1024);
+              float4 a1 = *reinterpret_cast<const float4*>(Ab + ((st * p.nrt + r0 + i) * 2 + 1) * 1024);
+              if (DZF) {
+                const float4 y0 = *reinterpret_cast<const float4*>(Ab + p.DYB + ((st * p.nrt + r0 + i) * 2) * 1024);
+                const float4 y1 = *reinterpret_cast<const float4*>(Ab + p.DYB + ((st * p.nrt + r0 + i) * 2 + 1) * 1024);
+                a0.x = bn_dy(a0.x, y0.x, i, live); a0.y = bn_dy(a0.y, y0.y, i, live);
+                a0.z = bn_dy(a0.z, y0.z, i, live); a0.w = bn_dy(a0.w, y0.w, i, live);
+                a1.x = bn_dy(a1.x, y1.x, i, live); a1.y = bn_dy(a1.y, y1.y, i, live);
+                a1.z = bn_dy(a1.z, y1.z, i, live); a1.w = bn_dy(a1.w, y1.w, i, live);
+              }
               if (MATH == 2) {
                 split_bf16x3(a0.x, a0.y, af[i][0].x, af[i][1].x, af[i][NP - 1].x);
                 split_bf16x3(a0.z, a0.w, af[i][0].y, af[i][1].y, af[i][NP - 1].y);
@@ -363,6 +419,22 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __rest
 }
 
 template <int MATH>
+__global__ __launch_bounds__(256) void conv_wgrad_stem_kernel(const void* __restrict__ x, const void* __restrict__ dy,
+                                                              float* __restrict__ slab, const StwParams p) {
+  stw_body<MATH, false>(x, dy, nullptr, nullptr, 0, slab, p);
+}
+
+// a second instantiation of the body: the plain kernel keeps its registers and its LDS
+// (two waves per SIMD = two workgroups per CU, as the plain kernel gets by itself: the bf16x6 form would otherwise take 272
+// registers and run alone on its CU)
+template <int MATH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv_wgrad_stem_dzf_kernel(const void* __restrict__ x, const void* __restrict__ dz,
+                                                                  const void* __restrict__ y, const float* __restrict__ consts,
+                                                                  const int relu, float* __restrict__ slab, const StwParams p) {
+  stw_body<MATH, true>(x, dz, y, consts, relu, slab, p);
+}
+
+template <int MATH>
 int launch_stw(dim3 grid, size_t lds, hipStream_t st, const void* x, const void* dy, float* slab, const StwParams& p) {
   static bool raised = false;
   if (lds > (48u << 10) && !raised) {
@@ -371,6 +443,19 @@ int launch_stw(dim3 grid, size_t lds, hipStream_t st, const void* x, const void*
     raised = true;
   }
   hipLaunchKernelGGL((conv_wgrad_stem_kernel<MATH>), grid, dim3(256), lds, st, x, dy, slab, p);
+  return gca_launch_status();
+}
+
+template <int MATH>
+int launch_stw_dzf(dim3 grid, size_t lds, hipStream_t st, const void* x, const void* dz, const void* y, const float* consts,
+                   int relu, float* slab, const StwParams& p) {
+  static bool raised = false;
+  if (lds > (48u << 10) && !raised) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_stem_dzf_kernel<MATH>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10) != hipSuccess) return GCA_ELAUNCH;
+    raised = true;
+  }
+  hipLaunchKernelGGL((conv_wgrad_stem_dzf_kernel<MATH>), grid, dim3(256), lds, st, x, dz, y, consts, relu, slab, p);
   return gca_launch_status();
 }
 
@@ -396,7 +481,8 @@ void stw_partition(const gca_conv_geom* g, int want, int& ohc, int& ohl, int& un
   splits = (int)gca_ceil_div(un, ups);
 }
 
-bool stw_params(const gca_conv_geom* g, int math, StwArgs& p, size_t& lds) {
+// dzf: the stage buffers hold dz AND y (gca_conv_wgrad_dzf) -- half the steps per stage, the same <= 16 pieces and the same bytes
+bool stw_params(const gca_conv_geom* g, int math, StwArgs& p, size_t& lds, bool dzf = false) {
   const int np = math == 2 ? 3 : (math == 1 ? 2 : 1);
   const int es = math == 3 ? 2 : 4;
   p.K = g->K; p.C = g->C; p.D = g->D; p.H = g->H; p.W = g->W; p.OD = g->OD; p.OH = g->OH; p.OW = g->OW;
@@ -416,7 +502,7 @@ bool stw_params(const gca_conv_geom* g, int math, StwArgs& p, size_t& lds) {
   p.ZB = (int)gca_round_up(np * 4 * p.ARRB, 16);
   // one dY stage: <= 16 pieces of 1 KB (<= 4 DMA instructions per wave)
   const int per_step = p.nrt * (es == 4 ? 2 : 1);
-  p.SS = 16 / per_step; if (p.SS > p.steps) p.SS = p.steps;
+  p.SS = 16 / (dzf ? 2 * per_step : per_step); if (p.SS > p.steps) p.SS = p.steps;
   if (p.SS < 1) return false;
   p.nstg = (int)gca_ceil_div(p.steps, p.SS);
   p.DYB = p.SS * per_step * 1024;
@@ -432,7 +518,7 @@ bool stw_params(const gca_conv_geom* g, int math, StwArgs& p, size_t& lds) {
   p.x_bytes = (unsigned)xb; p.dy_bytes = (unsigned)yb;
   p.nW = (long long)g->K * g->C * g->kd * g->kh * g->kw;
   p.slab_bytes = 0;
-  size_t need = (size_t)p.ZB + (size_t)p.g * p.PLS + 2 * (size_t)p.DYB;
+  size_t need = (size_t)p.ZB + (size_t)p.g * p.PLS + (dzf ? 4 : 2) * (size_t)p.DYB;
   const size_t red = (size_t)(p.wk - 1) * 2 * NT * 1024 * 4;
   if (red > need) need = red;
   lds = need;
@@ -463,6 +549,22 @@ bool wgrad_stem_plan(const gca_conv_geom* g, WgradLaunch& L) {
   L.dy_align = 16;
   L.xf = false;
   return true;
+}
+
+bool wgrad_stem_dzf_plan(const gca_conv_geom* g, WgradLaunch& L) {
+  if (L.kernel != WgradKernel::Stem) return false;
+  // Same partition, slabs and workgroups as the plain launch (stw_params is a pure function of g and the arithmetic); only the
+  // stage length and the LDS bytes change.  No geometry class is refused on measured grounds so far.
+  return stw_params(g, L.math, L.stw, L.lds, true) && L.stw.splits == L.splits;
+}
+
+int wgrad_stem_dzf_run(const WgradLaunch& L, const void* x, const void* dz, const void* y, const float* consts, int relu,
+                       float* slab, hipStream_t st) {
+  const StwParams p{L.stw};
+  const dim3 grid((unsigned)L.blocks);
+  if (L.math == 3) return launch_stw_dzf<3>(grid, L.lds, st, x, dz, y, consts, relu, slab, p);
+  if (L.math == 2) return launch_stw_dzf<2>(grid, L.lds, st, x, dz, y, consts, relu, slab, p);
+  return launch_stw_dzf<1>(grid, L.lds, st, x, dz, y, consts, relu, slab, p);
 }
 
 int wgrad_stem_run(const WgradLaunch& L, const void* x, const void* dy, float* slab, hipStream_t st) {

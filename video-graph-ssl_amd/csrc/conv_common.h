@@ -213,6 +213,11 @@ int wgrad_ts_run(const gca_conv_geom* g, const WgradLaunch& L, const float* x, c
 // conv3d_wgrad_stem.hip: the <= 4-channel, stride-2 stem kernel, same contract
 bool wgrad_stem_plan(const gca_conv_geom* g, WgradLaunch& L);
 int wgrad_stem_run(const WgradLaunch& L, const void* x, const void* dy, float* slab, hipStream_t st);
+// the same kernel forming dY from (dz, y, constants of gca_bn_bwd_sums) in registers: re-plans the stages of a Stem launch in L
+// (false: not a Stem launch, or the geometry is refused), then runs it
+bool wgrad_stem_dzf_plan(const gca_conv_geom* g, WgradLaunch& L);
+int wgrad_stem_dzf_run(const WgradLaunch& L, const void* x, const void* dz, const void* y, const float* consts, int relu,
+                       float* slab, hipStream_t st);
 inline bool unit_stride(const gca_conv_geom* g) { return g->sd == 1 && g->sh == 1 && g->sw == 1; }
 
 

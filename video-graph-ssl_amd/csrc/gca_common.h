@@ -14,6 +14,13 @@ static inline int gca_launch_status() {
 static inline int64_t gca_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t gca_round_up(int64_t a, int64_t b) { return gca_ceil_div(a, b) * b; }
 
+// Per-channel rows a consumer kernel reads whole 16-channel chunks of (scale / shift of the _xf entries, the constant array of
+// gca_bn_bwd_sums): a multiple of 16 floats + 16.
+__host__ __device__ inline int64_t gca_bn_consts_stride(int64_t C) { return (C + 15) / 16 * 16 + 16; }
+// Rows of gca_bn_bwd_sums' constant array: bn_bwd_apply_kernel's A = gamma * invstd, B = S1 / M, Cc = S2 / M, then mean, invstd
+// and the forward's (scale, shift) of ReLU mode 2 (zeros in mode 0).
+enum { GCA_BN_A = 0, GCA_BN_B, GCA_BN_CC, GCA_BN_MEAN, GCA_BN_INVSTD, GCA_BN_SCALE, GCA_BN_SHIFT, GCA_BN_BWD_CONST_ROWS };
+
 // Division of a 31-bit unsigned by a runtime constant without the ~40-instruction integer divide:
 // n / d == (umulhi(n, m) + ((n - umulhi(n, m)) >> 1)) >> (s - 1)   (Granlund-Montgomery round-up method).
 struct gca_magic { unsigned m; int s; unsigned d; };

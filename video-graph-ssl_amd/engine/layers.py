@@ -314,6 +314,18 @@ def f_conv_bn_act(tape, conv, bn, xv, relu=True, residual=None, out=None):
             # ReLU mask: with no residual in front of the ReLU it is recomputed from y (the forward's own scale/shift),
             # so z is not streamed again; with a residual the saved output is the only record
             mode = (2 if residual is None else 1) if relu else 0
+            # A first-layer conv (no gradient wrt its input) is the only reader of dy: the BatchNorm backward then stops at its
+            # sums and the stem weight-gradient kernel forms dy in registers from (dz, y) -- dy is never allocated.  fp32 storage
+            # only: on the fp16 3D-ResNet-50 stem the fused kernel grows by what the apply pass cost (39.94 -> 39.98 ms/step in a
+            # same-box A/B, inside the noise), so that path keeps the apply pass
+            if (ops.STEM_DZF and residual is None and xf is None and not xv.needs_grad and N * SP > BN_SMALL_ELEMS
+                    and x.dtype is torch.float32
+                    and DEBUG_GRADS is None and zv.grad.is_contiguous() and ops.conv_dzf_ok(plan)):
+                consts = ops.bn_bwd_sums(zv.grad, y, bn.weight.data, mean, invstd, mode, N, K, SP,
+                                         _grad_of(bn.weight), _grad_of(bn.bias), scale, shift)
+                ops.conv_wgrad_dzf(plan, x, zv.grad, y, consts, mode, _grad_of(conv.weight), accumulate=True)
+                zv.grad = None
+                return
             dy = ops.bn_bwd(zv.grad, z, y, bn.weight.data, mean, invstd, mode, N, K, SP,
                             _grad_of(bn.weight), _grad_of(bn.bias), dres, bool(racc), scale, shift)
             if DEBUG_GRADS is not None:          # diagnostics only: gradient wrt the conv output, per BN module

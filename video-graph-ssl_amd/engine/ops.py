@@ -419,13 +419,18 @@ class DeferredReduce(object):
             b = self.slabs[key] = torch.empty(max(int(plan.wgrad_ws), 16), dtype=torch.uint8, device=dw.device)
         return b
 
-    def add(self, plan, x, dy, dw, accumulate, xf=None):
+    def add(self, plan, x, dy, dw, accumulate, xf=None, dzf=None):
+        """dzf = (y, consts, relu): `dy` is dz, the gradient behind the conv's own BatchNorm (conv_wgrad_dzf)."""
         if any(j[1].data_ptr() == dw.data_ptr() for j in self.pending):
             self.flush()                                   # a weight used twice (SimSiam's two views): keep the += order, no race
         slab = self.slab_for(dw, plan)
         splits = C.c_int32(0)
-        H.call('gca_conv_wgrad_partial', plan.gp, _act(plan, x), ptr(xf[0]) if xf else None, ptr(xf[1]) if xf else None,
-               _act(plan, dy), ptr(plan.table(2)), slab.data_ptr(), C.addressof(splits), stream())
+        if dzf is not None:
+            H.call('gca_conv_wgrad_dzf_partial', plan.gp, _act(plan, x), _act(plan, dy), _act(plan, dzf[0]), ptr(dzf[1]),
+                   int(dzf[2]), ptr(plan.table(2)), slab.data_ptr(), C.addressof(splits), stream())
+        else:
+            H.call('gca_conv_wgrad_partial', plan.gp, _act(plan, x), ptr(xf[0]) if xf else None, ptr(xf[1]) if xf else None,
+                   _act(plan, dy), ptr(plan.table(2)), slab.data_ptr(), C.addressof(splits), stream())
         self.pending.append((slab, dw, dw.numel(), int(splits.value), int(bool(accumulate))))
 
     def flush(self):
@@ -472,6 +477,31 @@ def conv_wgrad(plan, x, dy, dw, accumulate=True, xf=None):
                int(accumulate), ptr(ws), stream())
         return dw
     _conv_wgrad_launch(plan, x, dy, dw, accumulate)
+    return dw
+
+
+# GCA_STEM_DZF=0: the first layer's BatchNorm backward writes dy and its weight gradient reads it back (A/B runs)
+STEM_DZF = os.environ.get('GCA_STEM_DZF', '1') != '0'
+
+
+def conv_dzf_ok(plan):
+    """True when, under the launch shape pinned in `plan`, the weight gradient runs on the stem kernel, which can form dy from
+    (dz, y, BatchNorm-backward constants) in registers: gca_conv_dzf_ok."""
+    return plan.tuned[2] and bool(H.lib.gca_conv_dzf_ok(plan.gp))
+
+
+def conv_wgrad_dzf(plan, x, dz, y, consts, relu, dw, accumulate=True):
+    """conv_wgrad against dy = BatchNorm backward of (dz, y) with the constants of bn_bwd_sums, never materialised
+    (gca_conv_wgrad_dzf; only where conv_dzf_ok(plan)).  relu: 0 or 2, as given to bn_bwd_sums."""
+    if not plan.tuned[2]:
+        raise RuntimeError('conv_wgrad_dzf needs a tuned plan (conv_dzf_ok)')
+    d = DEFER[0]
+    if d is not None and dw.is_contiguous():
+        d.add(plan, x, dz, dw, accumulate, dzf=(y, consts, relu))
+        return dw
+    ws = WS.get(plan.wgrad_ws, x.device)
+    H.call('gca_conv_wgrad_dzf', plan.gp, _act(plan, x), _act(plan, dz), _act(plan, y), ptr(consts), int(relu), ptr(plan.table(2)),
+           ptr(dw), int(accumulate), ptr(ws), stream())
     return dw
 
 
@@ -568,6 +598,16 @@ def bn_bwd(dz, z, x, gamma, mean, invstd, relu, N, Cc, SP, dgamma, dbeta, dres=N
            N, Cc, SP, aptr(dx), ptr(dgamma), ptr(dbeta), aptr(dres), int(dres_accumulate), _slice_stride(dz, Cc, SP),
            ptr(scale), ptr(shift), ptr(ws), is_half(dz, z if int(relu) == 1 else None, x, dres), stream())
     return dx
+
+
+def bn_bwd_sums(dz, x, gamma, mean, invstd, relu, N, Cc, SP, dgamma, dbeta, scale=None, shift=None):
+    """bn_bwd without its apply pass (relu 0 or 2): dgamma / dbeta accumulated as bn_bwd does, and -> the constant array
+    [7][16 * ceil(C / 16) + 16] from which conv_wgrad_dzf forms dx where it reads it."""
+    consts = torch.empty(H.lib.gca_bn_bwd_consts_elems(Cc), dtype=F32, device=x.device)
+    ws = WS.get(H.lib.gca_bn_bwd_ws_bytes(N, Cc, SP), x.device)
+    H.call('gca_bn_bwd_sums', aptr(dz), aptr(x), ptr(gamma), ptr(mean), ptr(invstd), int(relu), N, Cc, SP, ptr(dgamma), ptr(dbeta),
+           _slice_stride(dz, Cc, SP), ptr(scale), ptr(shift), ptr(consts), ptr(ws), is_half(dz, x), stream())
+    return consts
 
 
 # ----------------------------------------------------------------------------- pooling

@@ -133,6 +133,8 @@ class _TrainerBase(object):
             tape.backward(upto)
         finally:
             ops.DEFER[0] = None
+            # a pass that raised part-way leaves queued (slab, dw, +=) jobs behind: the next step must not fold them in
+            self._deferred.pending.clear()
 
     def _buckets_from_log(self, arena, log):
         """log: (backward closure index, parameter) pairs of one eager backward pass (engine.layers.GRAD_LOG).  Cuts the
