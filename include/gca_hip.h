@@ -441,6 +441,29 @@ int gca_clip_augment(const uint8_t* frames, int64_t b, int64_t views, int64_t T,
                      void* out, int out_f16, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Nearest-neighbour video retrieval (tools/video_retrieval.py:174-197: sklearn cosine_distances / euclidean_distances
+ * followed by np.argsort of every row of the (nq, ng) matrix, of which the first 50 entries are used).  Fused: the matrix
+ * is never written.  q (nq, D) and g (ng, D) contiguous fp32; metric 0 = cosine, 1 = euclidean; 1 <= k <= 64.
+ *   s = sum_d q[i,d] * g[j,d] on the fp32 matrix cores; squared row norms n2 by a pass of their own
+ *   cosine:    r = 1 / sqrt(n2) (both correctly rounded; 0 for an all-zero row), dist = 1 - (s * r_q) * r_g
+ *   euclidean: d2 = max(0, (n2_q + n2_g) - 2 s) is the ranking key, dist = sqrt(d2)
+ *   order:     ascending by (key, gallery index) -- np.argsort(kind='stable'); NaN keys after +inf, -0 counts as +0
+ *   idx (nq, k) int32 gallery rows, nearest first; dist (nq, k) fp32; with ng < k the tail is idx = -1, dist = +inf
+ *   q_label (nq) / g_label (ng) int64, both or neither: first_hit (nq) int32 = 1-based rank of the first returned row whose
+ *   label equals the query's, k + 1 if none (R@k' = mean(first_hit <= k') for every k' <= k).  Without labels first_hit is
+ *   not written.
+ * The gallery is cut into `slabs` contiguous slabs (0 = enough to fill the device, at most 64 and at most one per 128 rows);
+ * results are bitwise the same for every value.  ws: gca_retrieval_ws_bytes() bytes = the norms + nq * slabs_used * k * 8
+ * (instead of nq * ng * 4); ws_bytes is checked.  tests/retrieval_ref.py is the numpy statement of all of the above.
+ * GCA_EINVAL (nothing launched) for k outside [1, 64], D < 1, negative sizes or slabs, ng >= 2^31, another metric, labels
+ * on one side only, ws_bytes too small.  nq = 0 or ng = 0: nothing is launched and nothing written (the caller presets the
+ * tails).  Three launches: norms, per-slab top-k lists, merge. */
+int64_t gca_retrieval_ws_bytes(int64_t nq, int64_t ng, int64_t D, int32_t k, int32_t slabs);
+int gca_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, int64_t D, int32_t k, int32_t metric,
+                       const int64_t* q_label, const int64_t* g_label, int32_t slabs, int32_t* idx, float* dist,
+                       int32_t* first_hit, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-tensor parameter updates over flat, 256-element-aligned parameter arenas.
  * _momentum_update (tools/train_video_contrast_dis.py:177-180) and torch.optim.SGD as
  * configured by make_optimizer (lib/solver/build.py:24-59: one group per parameter).

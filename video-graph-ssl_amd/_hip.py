@@ -123,6 +123,9 @@ SIGNATURES = {
     'gca_clip_augment_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_clip_augment': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                  c_vp, c_i32, c_vp, c_vp]),
+    'gca_retrieval_ws_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i32]),
+    'gca_retrieval_topk': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                   c_i64, c_vp]),
     'gca_rank_ge': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     'gca_grad_unscale_clip': (c_i32, [c_vp, c_i64, c_f32, c_vp, c_f32, c_f32, c_i32, c_f32, c_vp, c_vp, c_vp]),
     'gca_scale_dev': (c_i32, [c_vp, c_i64, c_vp, c_f32, c_vp]),

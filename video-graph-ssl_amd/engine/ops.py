@@ -788,6 +788,53 @@ def queue_advance(ptr_dev, n, K):
     H.call('gca_queue_advance', ptr(ptr_dev), int(n), int(K), stream())
 
 
+# ----------------------------------------------------------------------------- retrieval
+RETRIEVAL_METRICS = {'cosine': 0, 'euclidean': 1}
+
+
+def retrieval_topk(q, g, k, metric='cosine', q_label=None, g_label=None, slabs=0):
+    """Nearest gallery rows of every query without the (nq, ng) distance matrix (tools/video_retrieval.py:174-197):
+    q (nq, D), g (ng, D) fp32 on the device -> (idx (nq, k) int32, dist (nq, k) fp32, first_hit (nq) int32 or None).
+    Ascending by (distance, gallery index); idx = -1 / dist = +inf past the end of a gallery shorter than k.  With int64
+    labels on both sides, first_hit is the 1-based rank of the first row of the query's class, k + 1 if none.  `slabs`
+    forces the number of gallery slabs (0 = fill the device); the result does not depend on it.  tests/retrieval_ref.py
+    states the arithmetic.  ValueError for arguments the kernel entry refuses."""
+    if metric not in RETRIEVAL_METRICS:
+        raise ValueError('retrieval_topk: metric must be one of %s (got %r)' % (sorted(RETRIEVAL_METRICS), metric))
+    if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise ValueError('retrieval_topk: q (nq, D) and g (ng, D) must share D (got %s, %s)' % (tuple(q.shape), tuple(g.shape)))
+    for lab, n in ((q_label, q.shape[0]), (g_label, g.shape[0])):
+        if lab is not None and (lab.dtype is not torch.int64 or lab.dim() != 1 or lab.shape[0] != n):
+            raise ValueError('retrieval_topk: labels are int64 vectors, one entry per row')
+    if (q_label is None) != (g_label is None):
+        raise ValueError('retrieval_topk: labels on both sides or on neither')
+    nq, D = q.shape
+    ng, k, slabs = g.shape[0], int(k), int(slabs)
+    if not -2 ** 31 <= k < 2 ** 31 or not -2 ** 31 <= slabs < 2 ** 31:
+        raise ValueError('retrieval_topk: k / slabs out of range')
+    nbytes = H.lib.gca_retrieval_ws_bytes(nq, ng, D, k, slabs)
+    if nbytes < 0:
+        raise ValueError('retrieval_topk: invalid arguments (nq=%d, ng=%d, D=%d, k=%d, slabs=%d)' % (nq, ng, D, k, slabs))
+    q, g = q.contiguous(), g.contiguous()
+    ql = None if q_label is None else q_label.contiguous()
+    gl = None if g_label is None else g_label.contiguous()
+    dev = q.device
+    labelled = ql is not None
+    if nq == 0 or ng == 0:         # nothing to search and nothing launched: every slot is tail
+        return (torch.full((nq, k), -1, dtype=torch.int32, device=dev), torch.full((nq, k), float('inf'), dtype=F32, device=dev),
+                torch.full((nq,), k + 1, dtype=torch.int32, device=dev) if labelled else None)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((nq, k), dtype=F32, device=dev)
+    hit = torch.empty((nq,), dtype=torch.int32, device=dev) if labelled else None
+    ws = WS.get(nbytes, dev)
+    rc = H.lib.gca_retrieval_topk(ptr(q), ptr(g), nq, ng, D, k, RETRIEVAL_METRICS[metric], ptr(ql), ptr(gl), slabs, ptr(idx),
+                                  ptr(dist), ptr(hit), ptr(ws), nbytes, stream())
+    if rc == -1:
+        raise ValueError('retrieval_topk: gca_retrieval_topk refused its arguments (labels on one side only?)')
+    H.check(rc, 'gca_retrieval_topk')
+    return idx, dist, hit
+
+
 # ----------------------------------------------------------------------------- graph block
 def graph_adj_fwd(gq, gk, u, max_hop, alpha, temperature):
     B, Ci, T = gq.shape[0], gq.shape[1], gq.shape[2]
