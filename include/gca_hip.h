@@ -464,6 +464,36 @@ int gca_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, i
                        int32_t* first_hit, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
+ * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
+ * bias (C) or NULL; target (b) int64.
+ *   logits[i,j] = (sum_d x[i,d] * w[j,d]) + bias[j]    fp32 matrix cores, fp32 accumulation, the bias added once at the end
+ *   row_lse[i]  = m_i + log sum_j exp(logits[i,j] - m_i), m_i the row maximum
+ *   rank_ge[i]  = gca_rank_ge of the stored logits;  loss[0] = (1/b) sum_i (row_lse[i] - logits[i,target[i]])
+ * target == NULL writes the logits only (and row_lse if given): the eval path.  rank_ge and loss may each be NULL; loss and
+ * rank_ge need target, target needs row_lse.  x == w == bias == NULL with a target: `logits` is an input and only the row
+ * statistics and the loss are computed (nn.CrossEntropyLoss of existing logits).
+ *   backward: g[i,j] = s (exp(logits[i,j] - row_lse[i]) - [j == target[i]]), s = gscale_host * (gscale_dev ? *gscale_dev : 1) / b,
+ *   formed on the fly;  dw[j,d] (+)= sum_i g[i,j] x[i,d];  dbias[j] (+)= sum_i g[i,j] (dbias may be NULL; `accumulate`
+ *   covers both);  dx[i,d] (+)= sum_j g[i,j] w[j,d], skipped for dx == NULL (linear probe).
+ * The target's column is found by comparing indices inside the sweep, never by address: a target outside [0, C) reads and
+ * writes nothing out of bounds (the row's results are unspecified; the host layer checks the labels).  No floating-point
+ * atomics, every sum in an order fixed by the shapes: outputs are bitwise the same from call to call.  At most three
+ * launches forward (tiles, row statistics, loss) and three backward (dw + dbias, for b > 512 the fold of its per-run slabs,
+ * dx), all on `stream`.  ws: gca_classifier_ws_bytes() bytes (one loss term per row, and for b > 512 ceil(b / 512) <= 16
+ * slabs of C * F + C floats); ws_bytes is checked.  tests/classify_ref.py is the fp64 statement of all of the above.
+ * GCA_EINVAL (nothing launched) for F < 1, C < 1, b < 0, a size of 2^31 or more, ws_bytes too small, loss or rank_ge without
+ * target, target without row_lse.  b == 0: returns 0, nothing launched. */
+int64_t gca_classifier_ws_bytes(int64_t b, int64_t F, int64_t C);
+int gca_classifier_fwd(const float* x, const float* w, const float* bias, const int64_t* target,
+                       int64_t b, int64_t F, int64_t C, float* logits, float* row_lse, int32_t* rank_ge,
+                       float* loss, void* ws, int64_t ws_bytes, void* stream);
+int gca_classifier_bwd(const float* x, const float* w, const float* logits, const float* row_lse,
+                       const int64_t* target, const float* gscale_dev, float gscale_host,
+                       int64_t b, int64_t F, int64_t C, float* dw, float* dbias, int accumulate,
+                       float* dx, int dx_accumulate, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-tensor parameter updates over flat, 256-element-aligned parameter arenas.
  * _momentum_update (tools/train_video_contrast_dis.py:177-180) and torch.optim.SGD as
  * configured by make_optimizer (lib/solver/build.py:24-59: one group per parameter).

@@ -12,11 +12,12 @@ raises if it has not been built -- there is no CPU fallback.
 """
 from . import _hip  # noqa: F401  (fails loudly when the HIP library is missing)
 from . import engine, lib, parallel  # noqa: F401
-from .engine.trainer import MoCoTrainer, SimSiamTrainer  # noqa: F401
+from .engine.trainer import ActionTrainer, MoCoTrainer, SimSiamTrainer  # noqa: F401
 from .lib import evaluation  # noqa: F401  (accuracy / AverageMeter, lib/evaluation/metric.py)
 from .lib.config import CfgNode, get_defaults  # noqa: F401
 from .lib.memory import create_contrast, create_criterion  # noqa: F401
-from .lib.modeling import create_visual_model  # noqa: F401
+from .lib.modeling import create_video_model, create_visual_model  # noqa: F401
+from .lib.utils import creat_criterion  # noqa: F401
 from .lib.solver import make_lr_scheduler, make_optimizer  # noqa: F401
 
 __version__ = '0.1.0'

@@ -162,6 +162,17 @@ class HipLinear(nn.Module, _PackedWeight):
         return ops.conv_plan((b, self.in_features, 1, 1, 1), self.out_features, 1, 1, 0, device)
 
 
+class HipClassifier(HipLinear):
+    """The class head of VideoModelWrapper (model_wrappers.py:99-117): nn.Linear's parameters with the reference's init,
+    normal_(weight, 0, 0.001) and a zero bias.  It runs through f_classifier, fused with the loss when there is a target;
+    as a backbone's `fc` it passes the pooled features on (f_head_fc) so that the wrapper can apply it."""
+
+    def __init__(self, fin, fout, std=0.001):
+        super().__init__(fin, fout, bias=True)
+        nn.init.normal_(self.weight, 0, std)
+        nn.init.constant_(self.bias, 0)
+
+
 class HipMaxPool3d(nn.Module):
     def __init__(self, kernel_size, stride=None, padding=0):
         super().__init__()
@@ -567,10 +578,43 @@ def f_l2norm(tape, xv):
     return yv
 
 
+def f_classifier(tape, lin, xv, target=None):
+    """The class head on pooled features xv (b, F) (model_wrappers.py:79-82).  Without `target`: the logits Var (one launch,
+    the eval path; there is no backward from bare logits).  With int64 labels (b,) on the device: the head and
+    mean cross-entropy fused (ops.classifier_fwd) -> (loss Var (1,), logits, row_lse, rank_ge); the closure forms the
+    softmax gradient on the fly, adds into the arena gradients of lin.weight / lin.bias and writes dx only when xv needs it.
+    The loss-gradient seed is loss Var's .grad if set (a 1-element device tensor), else 1.  Labels must lie in
+    [0, out_features): check them where their host copy is (the kernel never addresses memory by label)."""
+    x = xv.t
+    if target is None:
+        logits = ops.classifier_fwd(x, lin.weight.data, None if lin.bias is None else lin.bias.data)
+        yv = Var(logits, tape.recording)
+
+        def back_plain():
+            raise NotImplementedError('backward from bare logits is not built: pass the labels (f_classifier(..., target)) '
+                                      'and the head runs fused with its cross-entropy loss')
+        tape.record(back_plain)
+        return yv
+    logits, lse, rank, loss = ops.classifier_fwd(x, lin.weight.data, None if lin.bias is None else lin.bias.data, target)
+    lv = Var(loss, tape.recording)
+
+    def back():
+        seed, lv.grad = lv.grad, None
+        dx = dacc = None
+        if xv.needs_grad:
+            dx, dacc = xv.grad_buffer()
+        ops.classifier_bwd(x, lin.weight.data, logits, lse, target, _grad_of(lin.weight),
+                           None if lin.bias is None else _grad_of(lin.bias), True, dx, bool(dacc), gscale_dev=seed)
+    tape.record(back)
+    return lv, logits, lse, rank
+
+
 def f_head_fc(tape, fc, xv):
     """The backbone's last layer after VisualModelWrapper replaced it (visual_wrappers.py:107-110):
     Identity for DROPOUT == 0, otherwise whatever was left there."""
     if isinstance(fc, HipIdentity):
+        return xv
+    if isinstance(fc, HipClassifier):       # the class head: model_wrappers.VideoModelWrapper applies it (f_classifier)
         return xv
     if isinstance(fc, HipLinear):
         return f_linear(tape, fc, xv)

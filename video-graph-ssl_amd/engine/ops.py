@@ -835,6 +835,80 @@ def retrieval_topk(q, g, k, metric='cosine', q_label=None, g_label=None, slabs=0
     return idx, dist, hit
 
 
+# ----------------------------------------------------------------------------- class head
+def _classifier_args(x, w, bias, target, what):
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError('%s: x (b, F) and w (C, F) must share F (got %s, %s)' % (what, tuple(x.shape), tuple(w.shape)))
+    if bias is not None and tuple(bias.shape) != (w.shape[0],):
+        raise ValueError('%s: bias must be (C,)' % what)
+    if target is not None and (target.dtype is not torch.int64 or tuple(target.shape) != (x.shape[0],)):
+        raise ValueError('%s: target is an int64 vector, one label per row' % what)
+    b, Fd = x.shape
+    nbytes = H.lib.gca_classifier_ws_bytes(b, Fd, w.shape[0])
+    if nbytes < 0:
+        raise ValueError('%s: invalid sizes (b=%d, F=%d, C=%d)' % (what, b, Fd, w.shape[0]))
+    return b, Fd, w.shape[0], nbytes
+
+
+def classifier_fwd(x, w, bias=None, target=None, want_lse=False, want_rank=True, want_loss=True):
+    """Linear class head fused with softmax cross-entropy (gca_classifier_fwd; tests/classify_ref.py states the arithmetic).
+    x (b, F), w (C, F), bias (C) or None, fp32 on the device.  Without `target`: -> logits (b, C), or (logits, row_lse) with
+    want_lse (the eval path).  With int64 `target` (b,): -> (logits, row_lse, rank_ge | None, loss (1,) | None).  The labels
+    are NOT range-checked here (that needs their host copy: engine.layers.f_classifier's callers do it)."""
+    b, Fd, Cc, nbytes = _classifier_args(x, w, bias, target, 'classifier_fwd')
+    x, w = x.contiguous(), w.contiguous()
+    dev = x.device
+    logits = torch.empty((b, Cc), dtype=F32, device=dev)
+    train = target is not None
+    lse = torch.empty(b, dtype=F32, device=dev) if (train or want_lse) else None
+    rank = torch.empty(b, dtype=torch.int32, device=dev) if (train and want_rank) else None
+    loss = torch.empty(1, dtype=F32, device=dev) if (train and want_loss) else None
+    ws = WS.get(nbytes, dev)
+    H.call('gca_classifier_fwd', ptr(x), ptr(w), ptr(bias), ptr(target), b, Fd, Cc, ptr(logits), ptr(lse), ptr(rank), ptr(loss),
+           ptr(ws), nbytes, stream())
+    if train:
+        return logits, lse, rank, loss
+    return (logits, lse) if want_lse else logits
+
+
+def cross_entropy_fwd(logits, target):
+    """Row statistics and mean cross-entropy of existing (b, C) logits: gca_classifier_fwd without its product (x = w =
+    NULL).  -> (row_lse (b,), rank_ge (b,), loss (1,))."""
+    if logits.dim() != 2 or target.dtype is not torch.int64 or tuple(target.shape) != (logits.shape[0],):
+        raise ValueError('cross_entropy_fwd: (b, C) logits and int64 labels (b,)')
+    b, Cc = logits.shape
+    nbytes = H.lib.gca_classifier_ws_bytes(b, 1, Cc)
+    if nbytes < 0 or b == 0:
+        raise ValueError('cross_entropy_fwd: invalid sizes (b=%d, C=%d)' % (b, Cc))
+    logits = logits.contiguous()
+    dev = logits.device
+    lse, rank = torch.empty(b, dtype=F32, device=dev), torch.empty(b, dtype=torch.int32, device=dev)
+    loss = torch.empty(1, dtype=F32, device=dev)
+    ws = WS.get(nbytes, dev)
+    H.call('gca_classifier_fwd', None, None, None, ptr(target), b, 1, Cc, ptr(logits), ptr(lse), ptr(rank), ptr(loss), ptr(ws),
+           nbytes, stream())
+    return lse, rank, loss
+
+
+def classifier_bwd(x, w, logits, lse, target, dw, dbias=None, accumulate=True, dx=None, dx_accumulate=False, gscale_dev=None,
+                   gscale_host=1.0):
+    """d loss / d (w, bias, x) of classifier_fwd's mean cross-entropy times gscale_host * (*gscale_dev), the softmax gradient
+    formed on the fly (gca_classifier_bwd).  dw (C, F) and dbias (C) are written, or added to with `accumulate`; dx (b, F)
+    likewise with `dx_accumulate`, and dx=None skips that product altogether."""
+    b, Fd, Cc, nbytes = _classifier_args(x, w, dbias, target, 'classifier_bwd')
+    if tuple(logits.shape) != (b, Cc) or tuple(lse.shape) != (b,) or tuple(dw.shape) != (Cc, Fd) or target is None:
+        raise ValueError('classifier_bwd: logits (b, C), row_lse (b,), target (b,) and dw (C, F) are required')
+    if dx is not None and tuple(dx.shape) != (b, Fd):
+        raise ValueError('classifier_bwd: dx must be (b, F)')
+    for t in (logits, lse, dw, dbias, dx):
+        if t is not None and not t.is_contiguous():
+            raise ValueError('classifier_bwd: buffers must be contiguous')
+    x, w = x.contiguous(), w.contiguous()
+    ws = WS.get(nbytes, x.device)
+    H.call('gca_classifier_bwd', ptr(x), ptr(w), ptr(logits), ptr(lse), ptr(target), ptr(gscale_dev), float(gscale_host), b, Fd, Cc,
+           ptr(dw), ptr(dbias), int(bool(accumulate)), ptr(dx), int(bool(dx_accumulate)), ptr(ws), nbytes, stream())
+
+
 # ----------------------------------------------------------------------------- graph block
 def graph_adj_fwd(gq, gk, u, max_hop, alpha, temperature):
     B, Ci, T = gq.shape[0], gq.shape[1], gq.shape[2]

@@ -27,9 +27,12 @@ from .layers import BatchedPacker
 from .tape import Tape, Var
 from .. import parallel as par
 from ..lib.memory import create_contrast, create_criterion
-from ..lib.modeling import create_visual_model
+from ..lib.evaluation.metric import accuracy_from_rank
+from ..lib.evaluation.retrieval import encoder_state_dict
+from ..lib.modeling import create_video_model, create_visual_model
 from ..lib.solver import make_lr_scheduler, make_optimizer
-from ..lib.solver.build import clip_value_of
+from ..lib.solver.build import HipSGD, clip_value_of
+from ..lib.utils import creat_criterion
 
 
 def set_key_encoder_mode(model_ema):
@@ -581,3 +584,159 @@ class SimSiamTrainer(_TrainerBase):
         if self._packer is None:
             self._packer = BatchedPacker(self.model, (0, 1))
         return self.out
+
+
+class ActionTrainer(_TrainerBase):
+    """Action-recognition fine-tuning and linear probing of a (pre-trained) encoder: the iteration of the reference's
+    tools/train_ds.py:97-125 (train) and :170-190 (validation) on the HIP engine.  Eager, single GPU, fp32 storage.
+
+    Fine-tune (default): recording tape through the encoder and the fused class head (engine.layers.f_classifier), backward,
+    optional SOLVER.CLIP_GRADIENT, then make_optimizer(cfg, model)'s HipSGD over the whole model -- the reference's
+    one-group-per-parameter rules.
+
+    Linear probe (MODEL.LINEAR_PROBE): the encoder runs under model.train() on a non-recording tape, so nothing in it is
+    recorded or updated except the running statistics of its training-mode BatchNorms (tools/train_ds.py:81-84 freezes the
+    parameters, not the statistics); only the head is taped, and the optimizer is a HipSGD over the head alone (group names
+    `<prefix>fc.weight` / `<prefix>fc.bias`, same lr / weight-decay / bias rules).  The reference freezes every parameter
+    whose name lacks `new_fc`, which with MODEL.DROPOUT == 0 freezes the head too and trains nothing; here the probe trains
+    the head wherever it lives (base_model.fc or new_fc).
+
+    Not built, refused at construction: fine-tuning under partial BatchNorm (SOLVER.NO_PARTIALBN False: backward through an
+    eval-mode BatchNorm), fp16 storage, SOLVER.USE_TRICK, APEX.FLAG, more than one GPU, hipGraph capture."""
+
+    def __init__(self, cfg, device, seed=None, ctx=None, use_graph=False):
+        _check_unsupported(cfg)
+        if ops.ACT_F16[0]:
+            raise NotImplementedError('ActionTrainer runs on fp32 storage (ops.set_conv_math(\'fp16\') is active)')
+        if bool(cfg.SOLVER.USE_TRICK):
+            raise NotImplementedError('SOLVER.USE_TRICK (get_optim_policies, model_wrappers.py:150-213) is not built')
+        if ctx is not None and ctx.active:
+            raise NotImplementedError('ActionTrainer is single-GPU: an active DistCtx is not supported')
+        if use_graph:
+            raise NotImplementedError('ActionTrainer runs eagerly: hipGraph capture of the step is not built')
+        self.probe = bool(getattr(cfg.MODEL, 'LINEAR_PROBE', False))
+        if not self.probe and not bool(cfg.SOLVER.NO_PARTIALBN):
+            raise NotImplementedError('fine-tuning under partial BatchNorm (SOLVER.NO_PARTIALBN False) needs the backward '
+                                      'through eval-mode BatchNorm, which is not built; the linear probe accepts it')
+        if cfg.SOLVER.OPTIMIZER_NAME != 'SGD':
+            raise NotImplementedError('only SGD is built')
+        self.cfg, self.device = cfg, torch.device(device)
+        self.clip = clip_value_of(cfg)
+        self.criterion = creat_criterion(cfg)          # (validates MODEL.METRIC_LOSS_TYPE; the step runs it fused with the head)
+        if seed is not None:
+            torch.manual_seed(seed)
+        self.model = create_video_model(cfg)
+        self.model.to(self.device)
+        self.num_class = self.model.num_class
+        if self.probe:
+            head, prefix = self.model.classifier, self.model.classifier_prefix
+            for name, prm in self.model.named_parameters():
+                if not name.startswith(prefix):
+                    prm.requires_grad = False
+            groups = []
+            for key, value in head.named_parameters():
+                lr, wd = cfg.SOLVER.BASE_LR, cfg.SOLVER.WEIGHT_DECAY
+                if 'bias' in key:
+                    lr, wd = cfg.SOLVER.BASE_LR * cfg.SOLVER.BIAS_LR_FACTOR, cfg.SOLVER.WEIGHT_DECAY_BIAS
+                groups.append({'params': [value], 'lr': lr, 'weight_decay': wd, 'name': prefix + key})
+            self.optimizer = HipSGD(head, groups, momentum=cfg.SOLVER.MOMENTUM, nesterov=cfg.SOLVER.NESTEROV)
+        else:
+            arena_of(self.model)
+            self.optimizer = make_optimizer(cfg, self.model)
+        self.scheduler = make_lr_scheduler(cfg, self.optimizer)
+        self.model.train()
+        self.best_pred = 0.0
+        self._segments = None
+        self.out = {}
+
+    def load_pretrained(self, checkpoint):
+        """Encoder weights of a pre-training checkpoint (a path, or the dict the pre-training trainers write), loaded BY NAME:
+        the `encoder.base_model.*` entries of its state_dict go to `base_model.*` (lib.evaluation.encoder_state_dict).  The
+        reference zips model keys with checkpoint values by position (tools/train_ds.py:73-77); where that works it is the
+        same assignment.  The class head stays as initialised."""
+        if not isinstance(checkpoint, dict):
+            checkpoint = torch.load(checkpoint, map_location='cpu', weights_only=False)
+        prefix = self.model.classifier_prefix
+        enc = {k: v for k, v in encoder_state_dict(checkpoint['state_dict']).items() if not k.startswith(prefix)}
+        res = self.model.load_state_dict(enc, strict=False)
+        missing = [k for k in res.missing_keys if not k.startswith(prefix)]
+        if missing or res.unexpected_keys:
+            raise KeyError('pre-training checkpoint does not match the encoder: missing %s, unexpected %s'
+                           % (missing[:4], list(res.unexpected_keys)[:4]))
+        return self
+
+    def _labels(self, target, b):
+        """Range check on the host copy of the labels, then the int64 device vector.  (Device labels are copied back for the
+        check: pass host labels to avoid that sync.)"""
+        host = torch.as_tensor(target).detach().reshape(-1).to('cpu', torch.int64)
+        if host.numel() != b:
+            raise ValueError('one label per clip expected (got %d for %d clips)' % (host.numel(), b))
+        if b and (int(host.min()) < 0 or int(host.max()) >= self.num_class):
+            raise ValueError('labels must lie in [0, %d) (got %d .. %d)' % (self.num_class, int(host.min()), int(host.max())))
+        return host.to(self.device)
+
+    def _clips(self, images):
+        if images.device != self.device or images.dtype != torch.float32 or images.dim() != 5:
+            raise RuntimeError('fp32 clips (b, 3, T, H, W) already resident on %s are needed' % self.device)
+        return images.contiguous()
+
+    def train_step(self, images, target):
+        """images (b, 3, T, H, W) fp32 on the device, target (b,) integer labels -> dict of device tensors: loss (1,), logits
+        (b, C), rank_ge (b,), prec1 / prec5 (1,) in percent (accuracy(), tools/train_ds.py:120, from the fused ranks: no host
+        sync)."""
+        x = self._clips(images)
+        tgt = self._labels(target, x.shape[0])
+        if not self.model.training:
+            self.model.train()
+        self.optimizer._sync_tables()
+        self.optimizer.zero_grad()
+        if self.probe:
+            feat = self.model.features(Tape(False), Var(x))
+            tape = Tape(True)
+            lv, logits, _, rank = L.f_classifier(tape, self.model.classifier, Var(feat.t, False), tgt)
+        else:
+            tape = Tape(True)
+            lv, logits, _, rank = self.model.fwd_loss(tape, Var(x), tgt)
+        self._backward(tape, 0)
+        clip = None
+        if self.clip is not None:                      # tools/train_ds.py:113-116
+            clip = self.optimizer.clip_grad_norm(self.clip)
+        self.optimizer.step(grad_clip=clip)
+        prec1, prec5 = accuracy_from_rank(rank, (1, 5))
+        self.out = dict(loss=lv.t, logits=logits, rank_ge=rank, prec1=prec1, prec5=prec5)
+        if clip is not None:
+            self.out['grad_norm'] = clip
+        return self.out
+
+    def validate(self, batches):
+        """Eval mode, no tape (tools/train_ds.py:160-190): -> dict(loss, top1, top5, count), loss and accuracies (percent)
+        averaged by sample count.  One host sync, at the end."""
+        self.model.eval()
+        tot = torch.zeros(3, dtype=torch.float64, device=self.device)
+        n = 0
+        for images, target in batches:
+            x = self._clips(images.to(self.device))
+            tgt = self._labels(target, x.shape[0])
+            lv, _, _, rank = self.model.fwd_loss(Tape(False), Var(x), tgt)
+            b = x.shape[0]
+            tot += torch.stack([lv.t[0].double() * b, (rank < 1).sum().double(), (rank < 5).sum().double()])
+            n += b
+        self.model.train()
+        if n == 0:
+            raise ValueError('validate: no batches')
+        loss, c1, c5 = (float(v) for v in tot.cpu())
+        return dict(loss=loss / n, top1=100.0 * c1 / n, top5=100.0 * c5 / n, count=n)
+
+    def state_dict(self, epoch=0):
+        """The reference's checkpoint format (tools/train_ds.py:153-158): epoch, state_dict (the reference's model keys),
+        optimizer (torch.optim.SGD's wire format), best_pred.  In linear-probe mode the optimizer entry holds the class
+        head's two groups only -- the probe's optimizer has no others."""
+        return {'epoch': epoch, 'state_dict': self.model.state_dict(), 'optimizer': self.optimizer.state_dict(),
+                'best_pred': self.best_pred}
+
+    def load_state_dict(self, sd):
+        """Resume from state_dict() (bit-exact: parameters, BatchNorm buffers, momentum, learning rates) -> the epoch."""
+        self.model.load_state_dict(sd['state_dict'])
+        self.optimizer.load_state_dict(sd['optimizer'])
+        self.best_pred = float(sd.get('best_pred', 0.0))
+        return int(sd.get('epoch', 0))

@@ -71,7 +71,8 @@ def get_defaults():
     return CfgNode({
         'MODEL': dict(DEVICE='cuda', DEVICE_IDS='0, 1, 2, 3', SEED=1, BACKBONE='S3D', BACKBONE_TYPE='3D',
                       PRETRAINED=False, PRETRAIN_PATH='none', POOLING_TYPE='avg', DROPOUT=0.5,
-                      NO_PARTIALBN=False, DISTRIBUTED=True, AUG_FLAG=False),
+                      NO_PARTIALBN=False, DISTRIBUTED=True, AUG_FLAG=False, LINEAR_PROBE=False,
+                      METRIC_LOSS_TYPE='CrossEntropyLoss'),
         'INPUT': dict(BASE_SIZE=[224, 224], CROP_SIZE=[224, 224], MEAN=[0.485, 0.456, 0.406],
                       STD=[0.229, 0.224, 0.225], MODALITY='RGB', SAMPLE_TYPE='uniform', VIDEO_LENGTH=16,
                       FLIP=True, TEMPORAL_JITTER=False),
@@ -81,6 +82,7 @@ def get_defaults():
                        BIAS_LR_FACTOR=2, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, WEIGHT_DECAY_BIAS=0, NESTEROV=False,
                        USE_TRICK=False, LR_STEP=20, CLIP_GRADIENT='none', NO_PARTIALBN=True, GAMMA=0.1,
                        STEPS=(30, 60), WARMUP_FACTOR=1.0 / 3, WARMUP_ITERS=5, WARMUP_METHOD='linear'),
+        'TEST': dict(BATCH_SIZE=128, WEIGHT=''),
         'APEX': dict(FLAG=False, OPT_LEVEL='O1', LOCAL_RANK=-1),
         'CHECKPOINT': dict(RESUME='none', CHECKNAME='video_model', CHECKPOINT_INTERVAL=20, NO_VAL=False,
                            FINETUNE=False, PRINT_FREQ=20),

@@ -2,3 +2,5 @@ from .metric import AverageMeter, accuracy, accuracy_from_rank, rank_ge  # noqa:
 from .retrieval import (encoder_state_dict, extract_feature_single, extract_features, load_encoder,  # noqa: F401
                         recall_counts, topk_retrieval)
 from . import retrieval  # noqa: F401
+from .classify import eval_video, evaluate  # noqa: F401
+from . import classify  # noqa: F401

@@ -1,5 +1,6 @@
 """Model factory (reference: lib/modeling/build.py:16-32).  Same cfg keys, same return value."""
 from .graph_wrappers import GraphWrapper
+from .model_wrappers import VideoModelWrapper
 from .visual_wrappers import VisualModelWrapper
 
 
@@ -9,6 +10,14 @@ def _encoder(cfg):
                               dropout=cfg.MODEL.DROPOUT, partial_bn=not cfg.SOLVER.NO_PARTIALBN,
                               pretrained=cfg.MODEL.PRETRAINED, pretrain_path=cfg.MODEL.PRETRAIN_PATH,
                               aug_flag=bool(getattr(cfg.MODEL, 'AUG_FLAG', False)))
+
+
+def create_video_model(cfg):
+    """The downstream model (reference: lib/modeling/build.py:5-14): backbone + class head."""
+    return VideoModelWrapper(cfg.DATASET.NUM_CLASS, cfg.INPUT.VIDEO_LENGTH, cfg.INPUT.MODALITY, backbone_name=cfg.MODEL.BACKBONE,
+                             backbone_type=cfg.MODEL.BACKBONE_TYPE, agg_fun=cfg.MODEL.POOLING_TYPE, dropout=cfg.MODEL.DROPOUT,
+                             partial_bn=not cfg.SOLVER.NO_PARTIALBN, pretrained=cfg.MODEL.PRETRAINED,
+                             pretrain_path=cfg.MODEL.PRETRAIN_PATH)
 
 
 def create_visual_model(cfg):
