@@ -440,6 +440,36 @@ int gca_clip_augment(const uint8_t* frames, int64_t b, int64_t views, int64_t T,
                      const int32_t* divtab, const float* mean255, const float* inv_std255, int64_t H, int64_t W,
                      void* out, int out_f16, void* ws, void* stream);
 
+/* Downstream (action-recognition) views: many views of ONE decoded source per video (gca_clip_prepare and gca_clip_augment
+ * are unchanged).  Replaces the reference's host transforms for fine-tuning and testing and the H2D copy of every finished
+ * fp32 view:
+ *   training  VideoMultiScaleCrop -> VideoRandomHorizontalFlip -> VideoNormalize -> VideoToTensor
+ *             (lib/data/transform/build.py:27-35, consistency_transforms.py:366-468)
+ *   testing   VideoResize -> VideoCenterCrop | VideoFullResSample | VideoOverSampleCrop -> VideoNormalize -> VideoToTensor
+ *             (tools/test_ds.py:95-120, consistency_transforms.py:159-170, 341-349, 470-551)
+ * A crop of a resized uint8 frame is a window of the resize's tap table, so all test-time views of a video share one source
+ * and one table.  The arithmetic is the one written down in tests/views_ref.py (the resize of tests/augment_ref.py: two
+ * blends, one rounding shift to uint8; then (float(px) - m_c) * d_c, two fp32 roundings), reproduced bit for bit.  As for
+ * gca_clip_augment, parity with cv2's own rounding is UNVERIFIED and not claimed.
+ *   frames       : (n_src, F, Hs, Ws, 3) uint8, device: one decoded source per video (F = T for training, test_clips * T
+ *                  for testing); Hs, Ws <= 32767
+ *   records      : (n_views, 8) int32, device; records_host: the same words in HOST memory (they are validated there)
+ *                  0 src  1 t0  2 tab  3 oy  4 ox  5 flip  6, 7: 0
+ *   taps         : (n_tab, Lh + Lw, 4) int16, device, 8-byte aligned: Lh row taps, then Lw column taps, each {i0, i1, c0, c1}:
+ *                  two source indices in frame coordinates and their 11-bit weights, c0 + c1 = 2048
+ *   mean255, inv_std255 : HOST pointers to 3 floats each, as gca_clip_prepare
+ *   out          : (n_views, 3, T, H, W) fp32.  Pixel (y, x) of frame t of a view samples frames[src, t0 + t] through the row
+ *                  tap taps[tab, oy + y] and the column tap taps[tab, Lh + ox + (flip ? W - 1 - x : x)]
+ * GCA_EINVAL, with nothing launched and nothing written, for src outside [0, n_src), tab outside [0, n_tab), t0 < 0 or
+ * t0 + T > F, a window (oy, H) / (ox, W) outside (Lh) / (Lw), flip not 0 or 1, any size below 1, a tensor of 2^31 elements
+ * or more, T > 65535.  n_views = 0: returns 0, nothing launched.  The kernel clamps every index it forms from the device
+ * tables into its buffer: tap contents can mis-sample, never reach outside.  One launch, for any n_views. */
+int gca_clip_views(const uint8_t* frames, int64_t n_src, int64_t F, int64_t Hs, int64_t Ws,
+                   const int32_t* records_host, const int32_t* records, int64_t n_views,
+                   const int16_t* taps, int64_t n_tab, int64_t Lh, int64_t Lw,
+                   const float* mean255, const float* inv_std255,
+                   int64_t T, int64_t H, int64_t W, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Nearest-neighbour video retrieval (tools/video_retrieval.py:174-197: sklearn cosine_distances / euclidean_distances
  * followed by np.argsort of every row of the (nq, ng) matrix, of which the first 50 entries are used).  Fused: the matrix

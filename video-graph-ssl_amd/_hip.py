@@ -123,6 +123,8 @@ SIGNATURES = {
     'gca_clip_augment_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_clip_augment': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                  c_vp, c_i32, c_vp, c_vp]),
+    'gca_clip_views': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64,
+                               c_i64, c_vp, c_vp]),
     'gca_retrieval_ws_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i32]),
     'gca_retrieval_topk': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                    c_i64, c_vp]),

@@ -395,3 +395,318 @@ class DeviceInputStage(object):
         done.record(cur)
         self._consumed[staged.slot] = done
         return out
+
+
+# ---------------------------------------------------------------------------------------------- downstream views: host side
+# Action recognition feeds on other transforms than pre-training (lib/data/transform/build.py:27-35, tools/test_ds.py:95-120):
+# a multi-scale crop resized to the input size for training, and 1 / 3 / 5 / 10 crops of a resized frame times test_clips
+# temporal clips for testing.  Every view of a video is a window of ONE resized copy of its frames, and a crop of a resized
+# uint8 frame is a window of the resize's tap table -- so the host ships the decoded source once and gca_clip_views cuts all
+# views out of it.  tests/views_ref.py is the specification; the functions below are held equal to it.
+VIEW_REC = 8                      # int32 words per view record of gca_clip_views: src, t0, tab, oy, ox, flip, 0, 0
+MULTISCALE_SCALES = (1, .875, .75, .66)
+
+
+def _hw(size):
+    return (int(size), int(size)) if isinstance(size, (int, np.integer)) else (int(size[0]), int(size[1]))
+
+
+def _fix_offsets(more_fix_crop, image_w, image_h, crop_w, crop_h):
+    """VideoMultiScaleCrop.fill_fix_offset (consistency_transforms.py:446-468): (w, h) offsets as FLOATS, truncated by their
+    users."""
+    ws, hs = (image_w - crop_w) / 4, (image_h - crop_h) / 4
+    ret = [(0, 0), (4 * ws, 0), (0, 4 * hs), (4 * ws, 4 * hs), (2 * ws, 2 * hs)]
+    if more_fix_crop:
+        ret += [(0, 2 * hs), (4 * ws, 2 * hs), (2 * ws, 4 * hs), (2 * ws, 0 * hs), (1 * ws, 1 * hs), (3 * ws, 1 * hs),
+                (1 * ws, 3 * hs), (3 * ws, 3 * hs)]
+    return ret
+
+
+def sample_multiscale_crop(Hs, Ws, input_size, nprnd, rnd, scales=MULTISCALE_SCALES, max_distort=1, fix_crop=True,
+                           more_fix_crop=True, p_flip=0.5):
+    """Parameters of one training clip, drawn as VideoMultiScaleCrop._sample_crop_size + VideoRandomHorizontalFlip draw them
+    and in their order (consistency_transforms.py:405-436, 355-356): the crop pair, the fixed offset (or, fix_crop off, the two
+    randint(0, img - crop) draws), the flip.  nprnd: a np.random.RandomState (or np.random); rnd: a random.Random (or the
+    random module).  -> dict(y0, x0, ch, cw, flip).  The reference compares crop_h with input_size[1] and crop_w with
+    input_size[0] although it resizes to input_size[0] rows: kept as it is (every config is square)."""
+    size = _hw(input_size)
+    base = min(Ws, Hs)
+    sizes = [int(base * x) for x in scales]
+    crop_h = [size[1] if abs(x - size[1]) < 3 else x for x in sizes]
+    crop_w = [size[0] if abs(x - size[0]) < 3 else x for x in sizes]
+    pairs = [(w, h) for i, h in enumerate(crop_h) for j, w in enumerate(crop_w) if abs(i - j) <= max_distort]
+    cw, ch = pairs[nprnd.randint(len(pairs))]
+    if fix_crop:
+        offsets = _fix_offsets(more_fix_crop, Ws, Hs, cw, ch)
+        x0, y0 = offsets[nprnd.randint(len(offsets))]
+    else:
+        x0 = nprnd.randint(0, Ws - cw)
+        y0 = nprnd.randint(0, Hs - ch)
+    return dict(y0=int(y0), x0=int(x0), ch=int(ch), cw=int(cw), flip=bool(rnd.random() < p_flip))
+
+
+def test_view_layout(Hs, Ws, scale_size, crop_size, test_crops, test_clips, T):
+    """The views of ONE test video (tools/test_ds.py:95-114) -> (records (views, 8) int32 with src = 0, taps (1, Hr + Wr, 4)
+    int16): VideoResize(scale_size) as one tap table over the whole source frame, and one record per (crop origin, flip,
+    temporal clip), in that nesting (the order in which consistency_transforms.py:491-506 emits them).
+    test_crops 1: the central crop; 3: VideoFullResSample's left / right / centre at integer steps (:528-534); 5:
+    VideoOverSampleCrop's corners and centre at float steps truncated by int() (:489-495); 10: the same, each also flipped."""
+    (Hr, Wr), (H, W) = _hw(scale_size), _hw(crop_size)
+    if test_crops == 1:
+        origins, flips = [((Hr - H) // 2, (Wr - W) // 2)], (0,)
+    elif test_crops == 3:
+        ws, hs = (Wr - W) // 4, (Hr - H) // 4
+        origins, flips = [(2 * hs, 0), (2 * hs, 4 * ws), (2 * hs, 2 * ws)], (0,)
+    elif test_crops in (5, 10):
+        origins = [(int(oh), int(ow)) for ow, oh in _fix_offsets(False, Wr, Hr, W, H)]
+        flips = (0,) if test_crops == 5 else (0, 1)
+    else:
+        raise ValueError('only 1, 3, 5 and 10 test crops are supported, got %r' % (test_crops,))
+    if H < 1 or W < 1 or H > Hr or W > Wr or test_clips < 1 or T < 1:
+        raise ValueError('crop %r does not fit the resized frame %r' % ((H, W), (Hr, Wr)))
+    taps = np.concatenate([_resize_taps(0, Hs, Hr), _resize_taps(0, Ws, Wr)])[None]
+    rec = [(0, clip * T, 0, oy, ox, flip, 0, 0) for oy, ox in origins for flip in flips for clip in range(test_clips)]
+    return np.array(rec, dtype=np.int32), taps
+
+
+test_view_layout.__test__ = False          # (a name for the reference's test mode, not a test)
+
+
+def check_views(records, taps, Lh, n_src, F, Hs, Ws, T, H_out, W_out):
+    """ValueError for tables gca_clip_views would refuse (the entry checks the same record words and returns GCA_EINVAL) and
+    for tap indices outside the frame, which only the host checks (the kernel clamps them)."""
+    H, W = H_out, W_out
+    r, t = np.asarray(records), np.asarray(taps)
+    if r.ndim != 2 or r.shape[1] != VIEW_REC or t.ndim != 3 or t.shape[2] != 4 or t.shape[0] < 1:
+        raise ValueError('tables must be (n_views, 8) records and (n_tab, Lh + Lw, 4) taps')
+    if min(n_src, F, Hs, Ws, T, H, W) < 1 or max(Hs, Ws) > 32767:
+        raise ValueError('sizes must be >= 1 and source frames at most 32767 x 32767')
+    r = r.astype(np.int64)
+    n_tab, Lw = t.shape[0], t.shape[1] - Lh
+    if Lh < H or Lw < W:
+        raise ValueError('tap table (%d rows, %d columns) smaller than the output %r' % (Lh, Lw, (H, W)))
+    if ((r[:, 0] < 0) | (r[:, 0] >= n_src)).any() or ((r[:, 2] < 0) | (r[:, 2] >= n_tab)).any():
+        raise ValueError('record names a source outside [0, %d) or a table outside [0, %d)' % (n_src, n_tab))
+    if ((r[:, 1] < 0) | (r[:, 1] + T > F)).any():
+        raise ValueError('temporal clip outside the source: t0 + T > F = %d' % F)
+    if ((r[:, 3] < 0) | (r[:, 3] + H > Lh) | (r[:, 4] < 0) | (r[:, 4] + W > Lw)).any():
+        raise ValueError('window outside the tap table')
+    if ((r[:, 5] & ~1) != 0).any():
+        raise ValueError('flip must be 0 or 1')
+    rows, cols = t[:, :Lh, :2], t[:, Lh:, :2]
+    if rows.min() < 0 or rows.max() >= Hs or cols.min() < 0 or cols.max() >= Ws:
+        raise ValueError('tap index outside the source frame')
+
+
+def pack_views(views, n_src, F, Hs, Ws, T, H, W, out=None):
+    """The tables of one batch for clip_views / gca_clip_views -> (records (n_views, 8) int32, taps (n_tab, Lh + Lw, 4) int16,
+    Lh), checked.  `views` is one of
+      * a list of n_src dicts of sample_multiscale_crop (training): clip n is view n, reads source n through its own table,
+        whose taps map the crop box onto the (H, W) output; Lh = H;
+      * a dict(scale_size=, test_crops=, test_clips=) (testing): test_view_layout's records repeated for each of the n_src
+        videos, video-major, and its single table; Lh = the resized height; crop size = (H, W);
+      * (records, taps, Lh): tables made elsewhere, only checked.
+    ValueError for a crop box or a tap outside the frame, a window outside the table, t0 + T > F, an unsupported test_crops.
+    out: a (records, taps) pair of arrays to fill in place (the pinned buffers of ActionInputStage.acquire())."""
+    if isinstance(views, dict):
+        rec1, taps = test_view_layout(Hs, Ws, views['scale_size'], (H, W), views['test_crops'], views.get('test_clips', 1), T)
+        rec = np.tile(rec1, (n_src, 1))
+        rec[:, 0] = np.repeat(np.arange(n_src, dtype=np.int32), len(rec1))
+        Lh = _hw(views['scale_size'])[0]
+    elif isinstance(views, (tuple, list)) and len(views) == 3 and isinstance(views[0], np.ndarray):
+        rec, taps, Lh = np.ascontiguousarray(views[0], dtype=np.int32), np.ascontiguousarray(views[1], dtype=np.int16), int(views[2])
+    else:
+        if len(views) != n_src:
+            raise ValueError('one parameter dict per clip expected (got %d for %d clips)' % (len(views), n_src))
+        rec = np.zeros((n_src, VIEW_REC), dtype=np.int32)
+        taps = np.zeros((n_src, H + W, 4), dtype=np.int16)
+        for n, p in enumerate(views):
+            if p['ch'] < 1 or p['cw'] < 1 or p['y0'] < 0 or p['x0'] < 0 or p['y0'] + p['ch'] > Hs or p['x0'] + p['cw'] > Ws:
+                raise ValueError('crop box outside the source frame')
+            rec[n, :6] = (n, 0, n, 0, 0, int(bool(p['flip'])))
+            taps[n, :H] = _resize_taps(p['y0'], p['ch'], H)
+            taps[n, H:] = _resize_taps(p['x0'], p['cw'], W)
+        Lh = H
+    check_views(rec, taps, Lh, n_src, F, Hs, Ws, T, H, W)
+    if out is not None:
+        if out[0].shape != rec.shape or out[1].shape != taps.shape:
+            raise ValueError('out does not have the table shapes of this batch')
+        out[0][...] = rec
+        out[1][...] = taps
+        rec, taps = out
+    return rec, taps, Lh
+
+
+def clip_views(frames, tables, mean255, inv_std255, T, H_out, W_out, out=None, dev_tables=None):
+    """frames (n_src, F, Hs, Ws, 3) uint8 device tensor, tables = pack_views(...) = (records, taps, Lh) host arrays ->
+    (n_views, 3, T, H_out, W_out) fp32 through gca_clip_views.  dev_tables: (records, taps) already on the device (the stage
+    copies or keeps them there); the host taps may then be None, having been checked when they were packed.  Otherwise the
+    tables are checked here -- every record word the entry checks, and that every tap index lies inside the frame -- and
+    uploaded."""
+    if frames.dtype is not torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError('frames must be a contiguous (n_src, F, Hs, Ws, 3) uint8 tensor')
+    if not frames.is_cuda:
+        raise RuntimeError('clip_views needs the frames on the GPU (there is no CPU fallback)')
+    n_src, F, Hs, Ws, _ = frames.shape
+    rec, taps, Lh = tables
+    rec = np.ascontiguousarray(rec, dtype=np.int32)
+    if rec.ndim != 2 or rec.shape[1] != VIEW_REC:
+        raise ValueError('records must be (n_views, 8) int32')
+    dev = frames.device
+    if dev_tables is None:
+        taps = np.ascontiguousarray(taps, dtype=np.int16)
+        check_views(rec, taps, Lh, n_src, F, Hs, Ws, T, H_out, W_out)
+        dev_tables = (torch.from_numpy(rec).to(dev), torch.from_numpy(taps).to(dev))
+    drec, dtaps = dev_tables
+    if (drec.dtype is not torch.int32 or tuple(drec.shape) != rec.shape or dtaps.dtype is not torch.int16 or dtaps.dim() != 3
+            or dtaps.shape[2] != 4 or dtaps.shape[1] <= Lh or not drec.is_cuda or not dtaps.is_cuda
+            or not drec.is_contiguous() or not dtaps.is_contiguous()):
+        raise ValueError('device tables must be (n_views, 8) int32 records and (n_tab, Lh + Lw, 4) int16 taps on the GPU')
+    n_views, n_tab, Lw = rec.shape[0], dtaps.shape[0], dtaps.shape[1] - Lh
+    if out is None:
+        out = torch.empty((n_views, 3, T, H_out, W_out), dtype=torch.float32, device=dev)
+    elif (tuple(out.shape) != (n_views, 3, T, H_out, W_out) or not out.is_contiguous() or out.dtype is not torch.float32
+          or out.device != dev):
+        raise ValueError('out must be a contiguous (n_views, 3, T, H, W) fp32 tensor on the frames\' device')
+    m = np.ascontiguousarray(mean255, dtype=np.float32)
+    d = np.ascontiguousarray(inv_std255, dtype=np.float32)
+    H.call('gca_clip_views', frames.data_ptr(), n_src, F, Hs, Ws, rec.ctypes.data, drec.data_ptr(), n_views, dtaps.data_ptr(),
+           n_tab, Lh, Lw, m.ctypes.data, d.ctypes.data, T, H_out, W_out, out.data_ptr(), ops.stream())
+    return out
+
+
+class ActionInputStage(object):
+    """DeviceInputStage's pipeline for action recognition: decoded uint8 source frames in, (batch * views, 3, T, H, W) fp32
+    clips out through gca_clip_views; two pinned host buffers and two device buffers, the H2D copy on a copy stream, prepare()
+    on the compute stream behind an event.
+
+    mode='train': frames (batch, T, Hs, Ws, 3), one dict of sample_multiscale_crop per clip; the (records, taps) of a batch
+    travel with it in one small copy.  views = 1.
+    mode='test': frames (batch, test_clips * T, Hs, Ws, 3); the tap table of VideoResize(scale_size) and the records of the
+    test_crops x test_clips views of every video are built ONCE here and stay on the device: a batch ships frames only.
+    views = crops x test_clips (x 2 flips at test_crops = 10), video-major in the output.
+
+    Unlike DeviceInputStage, a slot whose batch has not been through prepare() is never handed out again: staging more
+    batches ahead than there are slots raises RuntimeError instead of overwriting a batch that is still waiting."""
+
+    def __init__(self, batch, frames_per_video, src_size, out_size, device, mode='train', scale_size=None, test_crops=1,
+                 test_clips=1, T=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), slots=2):
+        if mode not in ('train', 'test'):
+            raise ValueError('mode must be \'train\' or \'test\'')
+        self.mode, self.b, self.F = mode, int(batch), int(frames_per_video)
+        self.Hs, self.Ws = _hw(src_size)
+        self.H, self.W = _hw(out_size)
+        self.device = torch.device(device)
+        self.mean255, self.inv_std255 = normalize_constants(mean, std)
+        if mode == 'train':
+            self.T = self.F if T is None else int(T)
+            if self.T != self.F:
+                raise ValueError('training clips are the whole source: frames_per_video must equal T')
+            self.views, self.Lh, self.n_tab = 1, self.H, self.b
+            self._table_sizes = (self.b * VIEW_REC * 4, self.b * (self.H + self.W) * 8)
+            self._hostp = [torch.empty(sum(self._table_sizes), dtype=torch.uint8).pin_memory() for _ in range(slots)]
+            self._devp = [torch.empty(sum(self._table_sizes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
+        else:
+            if scale_size is None:
+                raise ValueError('test mode needs scale_size (VideoResize)')
+            self.T = self.F // int(test_clips) if T is None else int(T)
+            if self.T < 1 or self.T * int(test_clips) != self.F:
+                raise ValueError('frames_per_video must be test_clips * T')
+            spec = dict(scale_size=scale_size, test_crops=test_crops, test_clips=test_clips)
+            rec, taps, self.Lh = pack_views(spec, self.b, self.F, self.Hs, self.Ws, self.T, self.H, self.W)
+            self.views, self.n_tab = rec.shape[0] // self.b, 1
+            self._records = rec
+            self._dev_tables = (torch.from_numpy(rec).to(self.device), torch.from_numpy(taps).to(self.device))
+        shape = (self.b, self.F, self.Hs, self.Ws, 3)
+        self._host = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+        self._dev = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(slots)]
+        self._consumed = [None] * slots          # event recorded on the compute stream after the slot's kernel was issued
+        self._copied = [None] * slots            # event of the slot's last H2D copy (its pinned buffer is free after it)
+        self._pending = [False] * slots          # staged, not yet through prepare(): the slot must not be staged into
+        self._next = 0
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.frame_bytes = int(np.prod(shape))
+
+    def _tables(self, blob):
+        """(records, taps) views of one slot's table buffer (host or device); training mode."""
+        a = self._table_sizes[0]
+        return (blob[:a].view(torch.int32).view(self.b, VIEW_REC), blob[a:].view(torch.int16).view(self.b, self.H + self.W, 4))
+
+    def out_shape(self):
+        return (self.b * self.views, 3, self.T, self.H, self.W)
+
+    def acquire(self):
+        """-> (frames, tables): the pinned host buffers of the next slot for the loader to fill IN PLACE -- frames
+        (batch, F, Hs, Ws, 3) uint8 and, in training mode, the (records, taps) numpy views that
+        pack_views(params, ..., out=tables) fills (None in test mode).  RuntimeError if the slot still holds a batch that has
+        not been through prepare().  Blocks only if the slot's previous H2D copy is still in flight.  Follow with submit()."""
+        s = self._next
+        if self._pending[s]:
+            raise RuntimeError('all %d slots hold batches that have not been through prepare(): staging another one would '
+                               'overwrite a batch that is still waiting' % len(self._host))
+        if self._copied[s] is not None:
+            self._copied[s].synchronize()            # the pinned buffers of this slot are about to be overwritten by the host
+        if self.mode == 'train':
+            return self._host[s], tuple(t.numpy() for t in self._tables(self._hostp[s]))
+        return self._host[s], None
+
+    def submit(self, check=True):
+        """Start the asynchronous H2D copy of the slot handed out by the last acquire(); returns a StagedBatch."""
+        s = self._next
+        if self._pending[s]:
+            raise RuntimeError('slot %d holds a batch that has not been through prepare()' % s)
+        if self.mode == 'train':
+            hrec, htaps = (t.numpy() for t in self._tables(self._hostp[s]))
+            records = hrec.copy()                    # what the entry validates at prepare() time
+            if check:
+                check_views(records, htaps, self.Lh, self.b, self.F, self.Hs, self.Ws, self.T, self.H, self.W)
+        else:
+            records = self._records
+        self._next = (s + 1) % len(self._host)
+        with torch.cuda.stream(self.copy_stream):
+            if self._consumed[s] is not None:
+                self.copy_stream.wait_event(self._consumed[s])    # the kernel that read this device slot has been issued and passed
+            self._dev[s].copy_(self._host[s], non_blocking=True)
+            if self.mode == 'train':
+                self._devp[s].copy_(self._hostp[s], non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record(self.copy_stream)
+        self._copied[s] = ready
+        self._pending[s] = True
+        tables = self._tables(self._devp[s]) if self.mode == 'train' else self._dev_tables
+        return StagedBatch(self, s, self._dev[s], tables, ready, records)
+
+    def stage(self, frames, params=None):
+        """Convenience for callers that hold the batch elsewhere: frames (batch, F, Hs, Ws, 3) uint8 host tensor / ndarray and,
+        in training mode, one dict of sample_multiscale_crop per clip.  = acquire() + one host copy + submit()."""
+        f = torch.as_tensor(frames)
+        if tuple(f.shape) != tuple(self._host[0].shape) or f.dtype is not torch.uint8:
+            raise ValueError('frames must be uint8 of shape %r, got %s %r' % (tuple(self._host[0].shape), f.dtype, tuple(f.shape)))
+        if self.mode == 'train':
+            if params is None:
+                raise ValueError('training mode needs one parameter dict per clip')
+            # (packed before the slot is acquired: a refused record leaves the slot untouched)
+            rec, taps, _ = pack_views(params, self.b, self.F, self.Hs, self.Ws, self.T, self.H, self.W)
+            hf, (hrec, htaps) = self.acquire()
+            hrec[...] = rec
+            htaps[...] = taps
+        else:
+            if params is not None:
+                raise ValueError('test mode takes frames only: the views are fixed at construction')
+            hf, _ = self.acquire()
+        hf.copy_(f)
+        return self.submit(check=False)
+
+    def prepare(self, staged, out):
+        """Compute stream: wait for the copy, then all views of the batch into `out` (out_shape(), fp32)."""
+        if staged.stage is not self:
+            raise ValueError('batch was staged by another input stage')
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(staged.ready)
+        clip_views(staged.frames, (staged.records, None, self.Lh), self.mean255, self.inv_std255, self.T, self.H, self.W, out=out,
+                   dev_tables=staged.params)
+        done = torch.cuda.Event()
+        done.record(cur)
+        self._consumed[staged.slot] = done
+        self._pending[staged.slot] = False
+        return out

@@ -22,7 +22,7 @@ import torch
 from . import layers as L
 from . import ops
 from .arena import arena_of
-from .input import StagedBatch
+from .input import ActionInputStage, StagedBatch
 from .layers import BatchedPacker
 from .tape import Tape, Var
 from .. import parallel as par
@@ -647,6 +647,7 @@ class ActionTrainer(_TrainerBase):
         self.model.train()
         self.best_pred = 0.0
         self._segments = None
+        self._staged_clips = None                      # (b * views, 3, T, H, W) fp32: where staged batches are prepared
         self.out = {}
 
     def load_pretrained(self, checkpoint):
@@ -676,14 +677,26 @@ class ActionTrainer(_TrainerBase):
         return host.to(self.device)
 
     def _clips(self, images):
+        if isinstance(images, StagedBatch):
+            # uint8 source frames staged by engine.input.ActionInputStage: all views of the batch are cut, resized, flipped
+            # and normalised into a buffer the trainer keeps (gca_clip_views), then the step proceeds as on fp32 clips
+            stage = images.stage
+            if not isinstance(stage, ActionInputStage):
+                raise RuntimeError('ActionTrainer takes batches staged by an ActionInputStage')
+            if stage.device != self.device:
+                raise RuntimeError('batch was staged on %s, the trainer runs on %s' % (stage.device, self.device))
+            shape = stage.out_shape()
+            if self._staged_clips is None or tuple(self._staged_clips.shape) != shape:
+                self._staged_clips = torch.empty(shape, dtype=torch.float32, device=self.device)
+            return stage.prepare(images, self._staged_clips)
         if images.device != self.device or images.dtype != torch.float32 or images.dim() != 5:
             raise RuntimeError('fp32 clips (b, 3, T, H, W) already resident on %s are needed' % self.device)
         return images.contiguous()
 
     def train_step(self, images, target):
-        """images (b, 3, T, H, W) fp32 on the device, target (b,) integer labels -> dict of device tensors: loss (1,), logits
-        (b, C), rank_ge (b,), prec1 / prec5 (1,) in percent (accuracy(), tools/train_ds.py:120, from the fused ranks: no host
-        sync)."""
+        """images (b, 3, T, H, W) fp32 on the device -- or a StagedBatch of engine.input.ActionInputStage (uint8 source frames
+        on their way to the device) --, target (b,) integer labels -> dict of device tensors: loss (1,), logits (b, C), rank_ge
+        (b,), prec1 / prec5 (1,) in percent (accuracy(), tools/train_ds.py:120, from the fused ranks: no host sync)."""
         x = self._clips(images)
         tgt = self._labels(target, x.shape[0])
         if not self.model.training:
@@ -710,12 +723,12 @@ class ActionTrainer(_TrainerBase):
 
     def validate(self, batches):
         """Eval mode, no tape (tools/train_ds.py:160-190): -> dict(loss, top1, top5, count), loss and accuracies (percent)
-        averaged by sample count.  One host sync, at the end."""
+        averaged by sample count.  One host sync, at the end.  A batch is (fp32 clips | StagedBatch, labels)."""
         self.model.eval()
         tot = torch.zeros(3, dtype=torch.float64, device=self.device)
         n = 0
         for images, target in batches:
-            x = self._clips(images.to(self.device))
+            x = self._clips(images if isinstance(images, StagedBatch) else images.to(self.device))
             tgt = self._labels(target, x.shape[0])
             lv, _, _, rank = self.model.fwd_loss(Tape(False), Var(x), tgt)
             b = x.shape[0]

@@ -8,23 +8,38 @@ the whole (B, C) score block and is only right for batch size 1 -- the argmax is
 accuracy divides by the count of every class, NaN for a class that never occurs as a label -- the mean runs over the classes
 that do occur.
 
-Frame decoding, resizing and cropping stay a host transform, as in lib/evaluation/retrieval.py."""
+Two inputs: finished fp32 views made by a host transform (as in lib/evaluation/retrieval.py), or decoded uint8 frames
+staged by engine.input.ActionInputStage(mode='test'), whose resize, crops, flips and normalisation run on the device
+(gca_clip_views); only frame decoding then stays with the host."""
 import numpy as np
 import torch
 
+from ...engine.input import ActionInputStage, StagedBatch
 from ...engine.tape import Tape, Var
 from .metric import rank_ge
 from .retrieval import split_views
 
 
 def eval_video(model, data, num_crops, video_length, softmax=False):
-    """data (B, 3, clips * crops * T, H, W) -> video-level scores (B, num_class) on data's device: one eval-mode forward over
-    all clips x crops views, their mean, then optionally its softmax (tools/test_ds.py:134-149)."""
+    """data (B, 3, clips * crops * T, H, W), or a StagedBatch of a test-mode engine.input.ActionInputStage -> video-level
+    scores (B, num_class) on data's device: one eval-mode forward over all clips x crops views, their mean, then optionally its
+    softmax (tools/test_ds.py:134-149)."""
     if model.training:
         raise RuntimeError('eval_video needs the model in eval mode')
-    v = split_views(data, num_crops, video_length)
-    B, views = v.shape[:2]
-    x = v.reshape((B * views,) + tuple(v.shape[2:])).contiguous().float()
+    if isinstance(data, StagedBatch):
+        # uint8 source frames staged by a test-mode ActionInputStage: gca_clip_views writes the (B * views, 3, T, H, W) block
+        # the forward takes, video-major -- no split_views; num_crops / video_length are the stage's own
+        stage = data.stage
+        if not isinstance(stage, ActionInputStage) or stage.mode != 'test':
+            raise RuntimeError('eval_video takes batches staged by a test-mode ActionInputStage')
+        if video_length != stage.T:
+            raise ValueError('video_length %d, but the batch was staged as clips of %d frames' % (video_length, stage.T))
+        B, views = stage.b, stage.views
+        x = stage.prepare(data, torch.empty(stage.out_shape(), dtype=torch.float32, device=stage.device))
+    else:
+        v = split_views(data, num_crops, video_length)
+        B, views = v.shape[:2]
+        x = v.reshape((B * views,) + tuple(v.shape[2:])).contiguous().float()
     with torch.no_grad():
         out = model.fwd(Tape(False), Var(x, False)).t
         out = out.reshape(B, views, -1).mean(1)
@@ -60,7 +75,7 @@ def evaluate(model, batches, num_crops, video_length, softmax=False, device=None
     device = torch.device('cuda') if device is None else device
     scores, labels, hits, n = [], [], np.zeros(2), 0
     for data, label in batches:
-        s = eval_video(model, data.to(device), num_crops, video_length, softmax)
+        s = eval_video(model, data if isinstance(data, StagedBatch) else data.to(device), num_crops, video_length, softmax)
         lab = torch.as_tensor(label).reshape(-1).to(torch.int64)
         if lab.numel() != s.shape[0] or (lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= s.shape[1])):
             raise ValueError('one label in [0, %d) per video expected' % s.shape[1])
