@@ -537,6 +537,19 @@ int gca_ema_update(float* p_ema, const float* p, int64_t n, float m, void* strea
 int gca_sgd_step(float* p, const float* grad, float* mom_buf, int64_t n, const float* chunk_lr,
                  const float* chunk_wd, float lr_scale, float momentum, int nesterov, int first_step,
                  const float* grad_clip, void* stream);
+/* torch.optim.Adam (decoupled = 0) / AdamW (decoupled = 1), amsgrad = False, over the same arena layout and chunk tables
+ * as gca_sgd_step (n % 256 == 0), for step t = state[0] + 1:
+ *   g = grad * grad_clip[1];  Adam: g += wd * p   AdamW: p *= 1 - lr * wd
+ *   m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + (1 - beta2) * g * g
+ *   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * state: ONE int64 on the device, the number of steps taken.  gca_adam_step only reads it (the bias corrections are formed
+ * in fp64 from it inside the kernel); gca_adam_advance, a one-thread launch behind it, increments it -- so a captured
+ * hipGraph that replays both keeps counting.  0 <= beta < 1, eps > 0.  grad_clip as for gca_sgd_step: when grad_clip[2] != 0
+ * neither p, exp_avg, exp_avg_sq nor the step count change.  Padding elements (p = grad = m = v = 0) stay exactly 0. */
+int gca_adam_step(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* chunk_lr,
+                  const float* chunk_wd, double beta1, double beta2, double eps, int decoupled, const float* grad_clip,
+                  const int64_t* state, void* stream);
+int gca_adam_advance(int64_t* state, const float* grad_clip, void* stream);
 /* clip_grad_norm_(parameters, max_norm) of tools/train_video_contrast_dis.py:420-423 over the flat gradient arena
  * (n % 4 == 0; padding elements are zero): out4[0] = total 2-norm, out4[1] = min(1, max_norm / (norm + 1e-6)),
  * out4[2] = out4[3] = 0.  fp64 partial sums folded in a fixed order (deterministic); `ws` = gca_grad_clip_ws_bytes() bytes. */

@@ -1,5 +1,5 @@
 // Head pieces (ReLU, row L2-normalise, negative cosine) and the multi-tensor parameter updates
-// (EMA key-encoder update, SGD) over flat parameter arenas.  All HBM-bound float4 streaming.
+// (EMA key-encoder update, SGD, Adam / AdamW) over flat parameter arenas.  All HBM-bound float4 streaming.
 // Reference call sites: see include/gca_hip.h.
 #include <cstdint>
 #include "gca_common.h"
@@ -123,6 +123,60 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     reinterpret_cast<float4*>(p)[i] = pv;
     reinterpret_cast<float4*>(buf)[i] = bv;
   }
+}
+
+// torch.optim.Adam / AdamW (amsgrad=False, maximize=False) for step t = state[0] + 1, one pass over the arena:
+//   g = grad * coef;   Adam: g += wd*p   AdamW: p *= 1 - lr*wd
+//   m = b1*m + (1-b1)*g;   v = b2*v + (1-b2)*g*g;   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// The number of steps taken lives on the device (state[0], an exact integer that adam_advance_kernel increments behind
+// this kernel): a t passed by the host would be frozen into a captured hipGraph and with it the bias corrections.
+// 1 - beta^t is formed in fp64 from that integer by every thread (repeated squaring: at most 2 * 63 multiplications next to the
+// HBM traffic of its share of the arena) -- in fp32, 1 - 0.999f^1 has already lost four digits to cancellation.
+__device__ inline double adam_one_minus_pow(double beta, long long t) {
+  double r = 1.0, b = beta;
+  for (unsigned long long e = (unsigned long long)t; e; e >>= 1) {
+    if (e & 1) r *= b;
+    b *= b;
+  }
+  return 1.0 - r;
+}
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, long long n4, const float* __restrict__ clr,
+                                                   const float* __restrict__ cwd, double beta1, double beta2, float eps,
+                                                   int decoupled, const float* __restrict__ gscale,
+                                                   const long long* __restrict__ state) {
+  if (gscale && gscale[2] != 0.f) return;          // non-finite gradient under loss scaling: optimizer.step() is skipped
+  const float gs = gscale ? gscale[1] : 1.f;
+  const long long t = state[0] + 1;
+  const float inv_bc1 = (float)(1.0 / adam_one_minus_pow(beta1, t));
+  const float inv_bc2s = (float)(1.0 / sqrt(adam_one_minus_pow(beta2, t)));
+  // 1 - beta from the fp64 beta: 1.f - 0.999f is 1.3e-5 (relative) away from 0.001
+  const float b1 = (float)beta1, b2 = (float)beta2, ob1 = (float)(1.0 - beta1), ob2 = (float)(1.0 - beta2);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const long long c = i >> 6;
+    const float lr = clr[c], wd = cwd[c];
+    const float ss = lr * inv_bc1, keep = 1.f - lr * wd;
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    if (gscale) { gv.x *= gs; gv.y *= gs; gv.z *= gs; gv.w *= gs; }
+    float d;
+#define GCA_ADAM1(f)                                  \
+    d = gv.f;                                         \
+    if (decoupled) pv.f *= keep; else d += wd * pv.f; \
+    mv.f = b1 * mv.f + ob1 * d;                       \
+    vv.f = b2 * vv.f + ob2 * (d * d);                 \
+    pv.f -= ss * (mv.f / (sqrtf(vv.f) * inv_bc2s + eps));
+    GCA_ADAM1(x) GCA_ADAM1(y) GCA_ADAM1(z) GCA_ADAM1(w)
+#undef GCA_ADAM1
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+}
+__global__ void adam_advance_kernel(long long* __restrict__ state, const float* __restrict__ gscale) {
+  if (threadIdx.x == 0 && !(gscale && gscale[2] != 0.f)) state[0] += 1;      // a skipped step is not counted
 }
 
 // clip_grad_norm_ (tools/train_video_contrast_dis.py:420-423; torch.nn.utils.clip_grad_norm_, 2-norm): per-block partial
@@ -279,6 +333,22 @@ int gca_sgd_step(float* p, const float* grad, float* mom_buf, int64_t n, const f
   if (!p || !grad || !mom_buf || !chunk_lr || !chunk_wd || n <= 0 || (n & 255)) return GCA_EINVAL;
   hipLaunchKernelGGL(sgd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p, grad, mom_buf,
                      (long long)(n / 4), chunk_lr, chunk_wd, lr_scale, momentum, nesterov, first_step, grad_clip);
+  return gca_launch_status();
+}
+int gca_adam_step(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* chunk_lr,
+                  const float* chunk_wd, double beta1, double beta2, double eps, int decoupled, const float* grad_clip,
+                  const int64_t* state, void* stream) {
+  if (!p || !grad || !exp_avg || !exp_avg_sq || !chunk_lr || !chunk_wd || !state || n <= 0 || (n & 255) ||
+      !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
+    return GCA_EINVAL;
+  hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p, grad, exp_avg, exp_avg_sq,
+                     (long long)(n / 4), chunk_lr, chunk_wd, beta1, beta2, (float)eps, decoupled ? 1 : 0, grad_clip,
+                     (const long long*)state);
+  return gca_launch_status();
+}
+int gca_adam_advance(int64_t* state, const float* grad_clip, void* stream) {
+  if (!state) return GCA_EINVAL;
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long*)state, grad_clip);
   return gca_launch_status();
 }
 int64_t gca_grad_clip_ws_bytes(void) { return (int64_t)CLIP_BLOCKS * (int64_t)sizeof(double); }

@@ -958,6 +958,16 @@ def sgd_step(p, g, buf, chunk_lr, chunk_wd, lr_scale, momentum, nesterov, grad_c
            float(momentum), int(nesterov), 0, ptr(grad_clip), stream())
 
 
+def adam_step(p, g, exp_avg, exp_avg_sq, chunk_lr, chunk_wd, beta1, beta2, eps, decoupled, state, grad_clip=None):
+    """One Adam (decoupled False) / AdamW (True) step over the arena, then the step count `state` (one int64 on the device,
+    steps taken so far) is advanced by a launch of its own; a set skip flag in `grad_clip` leaves all of it untouched."""
+    if state.dtype is not torch.int64 or state.numel() != 1:
+        raise TypeError('the Adam step count is one int64 on the device')
+    H.call('gca_adam_step', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_avg_sq), p.numel(), ptr(chunk_lr), ptr(chunk_wd),
+           float(beta1), float(beta2), float(eps), int(bool(decoupled)), ptr(grad_clip), ptr(state), stream())
+    H.call('gca_adam_advance', ptr(state), ptr(grad_clip), stream())
+
+
 def grad_clip_coef(g, max_norm, out=None):
     """clip_grad_norm_ over the flat gradient arena -> device tensor (total_norm, clip coefficient, 0, 0)."""
     if out is None:

@@ -31,7 +31,7 @@ from ..lib.evaluation.metric import accuracy_from_rank
 from ..lib.evaluation.retrieval import encoder_state_dict
 from ..lib.modeling import create_video_model, create_visual_model
 from ..lib.solver import make_lr_scheduler, make_optimizer
-from ..lib.solver.build import HipSGD, clip_value_of
+from ..lib.solver.build import check_optimizer_name, clip_value_of
 from ..lib.utils import creat_criterion
 
 
@@ -585,18 +585,33 @@ class SimSiamTrainer(_TrainerBase):
             self._packer = BatchedPacker(self.model, (0, 1))
         return self.out
 
+    def state_dict(self, epoch=0):
+        """Checkpoint dict with the reference's keys (tools/...dis.py:274-286; SimSiam has no memory, so `contrast` is None
+        as the reference writes it).  ActionTrainer.load_pretrained and lib.evaluation.load_encoder read its `state_dict`."""
+        return {'epoch': epoch, 'state_dict': self.model.state_dict(), 'optimizer': self.optimizer.state_dict(), 'contrast': None,
+                **({} if self.scale_state is None else {'loss_scale_state': self.scale_state.detach().cpu().clone()})}
+
+    def load_state_dict(self, sd):
+        """Resume from state_dict() (bit-exact: parameters, BatchNorm buffers, optimizer state, learning rates) or from a
+        reference checkpoint -> the epoch."""
+        self.model.load_state_dict(sd['state_dict'])
+        self.optimizer.load_state_dict(sd['optimizer'])
+        if self.scale_state is not None and sd.get('loss_scale_state') is not None:
+            self.scale_state.copy_(sd['loss_scale_state'])
+        return int(sd.get('epoch', 0))
+
 
 class ActionTrainer(_TrainerBase):
     """Action-recognition fine-tuning and linear probing of a (pre-trained) encoder: the iteration of the reference's
     tools/train_ds.py:97-125 (train) and :170-190 (validation) on the HIP engine.  Eager, single GPU, fp32 storage.
 
     Fine-tune (default): recording tape through the encoder and the fused class head (engine.layers.f_classifier), backward,
-    optional SOLVER.CLIP_GRADIENT, then make_optimizer(cfg, model)'s HipSGD over the whole model -- the reference's
-    one-group-per-parameter rules.
+    optional SOLVER.CLIP_GRADIENT, then make_optimizer(cfg, model)'s HipSGD / HipAdam over the whole model -- the
+    reference's one-group-per-parameter rules.
 
     Linear probe (MODEL.LINEAR_PROBE): the encoder runs under model.train() on a non-recording tape, so nothing in it is
     recorded or updated except the running statistics of its training-mode BatchNorms (tools/train_ds.py:81-84 freezes the
-    parameters, not the statistics); only the head is taped, and the optimizer is a HipSGD over the head alone (group names
+    parameters, not the statistics); only the head is taped, and the optimizer is make_optimizer's over the head alone (group names
     `<prefix>fc.weight` / `<prefix>fc.bias`, same lr / weight-decay / bias rules).  The reference freezes every parameter
     whose name lacks `new_fc`, which with MODEL.DROPOUT == 0 freezes the head too and trains nothing; here the probe trains
     the head wherever it lives (base_model.fc or new_fc).
@@ -618,8 +633,7 @@ class ActionTrainer(_TrainerBase):
         if not self.probe and not bool(cfg.SOLVER.NO_PARTIALBN):
             raise NotImplementedError('fine-tuning under partial BatchNorm (SOLVER.NO_PARTIALBN False) needs the backward '
                                       'through eval-mode BatchNorm, which is not built; the linear probe accepts it')
-        if cfg.SOLVER.OPTIMIZER_NAME != 'SGD':
-            raise NotImplementedError('only SGD is built')
+        check_optimizer_name(cfg)
         self.cfg, self.device = cfg, torch.device(device)
         self.clip = clip_value_of(cfg)
         self.criterion = creat_criterion(cfg)          # (validates MODEL.METRIC_LOSS_TYPE; the step runs it fused with the head)
@@ -633,13 +647,7 @@ class ActionTrainer(_TrainerBase):
             for name, prm in self.model.named_parameters():
                 if not name.startswith(prefix):
                     prm.requires_grad = False
-            groups = []
-            for key, value in head.named_parameters():
-                lr, wd = cfg.SOLVER.BASE_LR, cfg.SOLVER.WEIGHT_DECAY
-                if 'bias' in key:
-                    lr, wd = cfg.SOLVER.BASE_LR * cfg.SOLVER.BIAS_LR_FACTOR, cfg.SOLVER.WEIGHT_DECAY_BIAS
-                groups.append({'params': [value], 'lr': lr, 'weight_decay': wd, 'name': prefix + key})
-            self.optimizer = HipSGD(head, groups, momentum=cfg.SOLVER.MOMENTUM, nesterov=cfg.SOLVER.NESTEROV)
+            self.optimizer = make_optimizer(cfg, head, name_prefix=prefix)
         else:
             arena_of(self.model)
             self.optimizer = make_optimizer(cfg, self.model)
@@ -742,7 +750,7 @@ class ActionTrainer(_TrainerBase):
 
     def state_dict(self, epoch=0):
         """The reference's checkpoint format (tools/train_ds.py:153-158): epoch, state_dict (the reference's model keys),
-        optimizer (torch.optim.SGD's wire format), best_pred.  In linear-probe mode the optimizer entry holds the class
+        optimizer (torch.optim.SGD's / Adam's wire format), best_pred.  In linear-probe mode the optimizer entry holds the class
         head's two groups only -- the probe's optimizer has no others."""
         return {'epoch': epoch, 'state_dict': self.model.state_dict(), 'optimizer': self.optimizer.state_dict(),
                 'best_pred': self.best_pred}
