@@ -537,6 +537,31 @@ int gca_ema_update(float* p_ema, const float* p, int64_t n, float m, void* strea
 int gca_sgd_step(float* p, const float* grad, float* mom_buf, int64_t n, const float* chunk_lr,
                  const float* chunk_wd, float lr_scale, float momentum, int nesterov, int first_step,
                  const float* grad_clip, void* stream);
+/* LARS (apex LARC(clip = False) around torch.optim.SGD, dampening 0) over the same arena layout and chunk tables as
+ * gca_sgd_step (n % 256 == 0).  For tensor i with weights w, its chunks' lr / wd, coef = grad_clip[1] (1 without a record):
+ *   g = grad * coef;  nw = ||w||_2;  ng = ||g||_2 = coef * ||grad||_2
+ *   q = trust_coef * nw / (ng + wd * nw + eps)   if adapt[i] and nw > 0 and ng > 0, else 1
+ *   d = q * (g + wd * w);  buf = momentum * buf + d;  w -= lr * (nesterov ? d + momentum * buf : buf)
+ * Three launches on `stream`, no host sync, no atomics, every sum in a fixed order (bit-reproducible):
+ *   1. one workgroup per job sums w^2 and grad^2 in fp64 -> partials[2 * job], partials[2 * job + 1];
+ *   2. one workgroup per tensor folds its jobs' partials in job order, writes norms[2 * i] = nw, norms[2 * i + 1] = ng (fp64),
+ *      forms q in fp64, rounds it once to fp32 and writes trust[i] and chunk_trust[c] for every chunk c of the tensor;
+ *   3. gca_sgd_step's kernel with the per-chunk factor q, in the order written above.
+ * Host tables, int32, built once per arena and resident on the device:
+ *   jobs   [n_jobs][3]   (tensor, first chunk, chunk count <= gca_lars_job_chunks()); a job lies inside ONE tensor, the jobs
+ *                        of a tensor are consecutive and in chunk order, every chunk of the arena is in exactly one job
+ *   params [n_params][4] (first job, job count, first chunk, chunk count) of every tensor
+ *   adapt  [n_params]    non-zero: the tensor takes the trust ratio (torch-side rule: p.ndim > 1)
+ * The library cannot see inside them: indices out of range are out-of-bounds accesses.  partials: 2 * n_jobs doubles;
+ * norms: 2 * n_params doubles; trust: n_params floats; chunk_trust: n / 256 floats.  trust_coef > 0, eps >= 0,
+ * 0 <= momentum < 1.  grad_clip as for gca_sgd_step, read on the device by all three launches: when grad_clip[2] != 0
+ * neither p, mom_buf, norms, trust nor chunk_trust change.  Padding elements (p = grad = buf = 0) stay exactly 0.  A tensor
+ * with q == 1 takes gca_sgd_step's (lr_scale = 1) operations bit for bit. */
+int gca_lars_job_chunks(void);
+int gca_lars_step(float* p, const float* grad, float* mom_buf, int64_t n, const float* chunk_lr, const float* chunk_wd,
+                  const int32_t* jobs, int64_t n_jobs, const int32_t* params, const int32_t* adapt, int64_t n_params,
+                  double* partials, double* norms, float* trust, float* chunk_trust, float momentum, int nesterov,
+                  double trust_coef, double eps, const float* grad_clip, void* stream);
 /* torch.optim.Adam (decoupled = 0) / AdamW (decoupled = 1), amsgrad = False, over the same arena layout and chunk tables
  * as gca_sgd_step (n % 256 == 0), for step t = state[0] + 1:
  *   g = grad * grad_clip[1];  Adam: g += wd * p   AdamW: p *= 1 - lr * wd

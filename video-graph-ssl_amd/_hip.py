@@ -102,6 +102,9 @@ SIGNATURES = {
     'gca_graph_gcn_bwd': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     'gca_ema_update': (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp]),
     'gca_sgd_step': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_f32, c_i32, c_i32, c_vp, c_vp]),
+    'gca_lars_job_chunks': (c_i32, []),
+    'gca_lars_step': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32,
+                              c_i32, c_f64, c_f64, c_vp, c_vp]),
     'gca_adam_step': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp]),
     'gca_adam_advance': (c_i32, [c_vp, c_vp, c_vp]),
     'gca_grad_clip_ws_bytes': (c_i64, []),

@@ -1,5 +1,5 @@
 // Head pieces (ReLU, row L2-normalise, negative cosine) and the multi-tensor parameter updates
-// (EMA key-encoder update, SGD, Adam / AdamW) over flat parameter arenas.  All HBM-bound float4 streaming.
+// (EMA key-encoder update, SGD, LARS, Adam / AdamW) over flat parameter arenas.  All HBM-bound float4 streaming.
 // Reference call sites: see include/gca_hip.h.
 #include <cstdint>
 #include "gca_common.h"
@@ -97,17 +97,28 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ pe, const 
   }
 }
 
+// The LARS factor times d, rounded on its own (the pragma withholds the product from contraction): fused into
+// mom * buf + q * d it would round mom * buf instead, and a tensor with q == 1 would leave the SGD kernel's bits.
+__device__ __forceinline__ float lars_scaled(float q, float d) {
+#pragma clang fp contract(off)
+  return q * d;
+}
+
 // torch.optim.SGD: d = g + wd*p; buf = (first ? d : mom*buf + d); d = nesterov ? d + mom*buf : buf; p -= lr*d
 // One 256-element chunk per (lr, wd) pair: chunk c = i4 / 64.
+// TRUST (LARS, gca_lars_step): d = ctr[c] * (g + wd*p), one more per-chunk factor (the tensor's trust ratio, written by
+// lars_trust_kernel); the SGD instantiation never touches ctr and compiles to the operations it had without the parameter.
+template <bool TRUST>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                   long long n4, const float* __restrict__ clr, const float* __restrict__ cwd,
                                                   float lr_scale, float mom, int nesterov, int first,
-                                                  const float* __restrict__ gscale) {
+                                                  const float* __restrict__ gscale, const float* __restrict__ ctr) {
   const float gs = gscale ? gscale[1] : 1.f;       // clip coefficient of gca_grad_clip_coef (grads.mul_(coef) folded in)
   if (gscale && gscale[2] != 0.f) return;          // a non-finite gradient was found (gca_grad_unscale_clip): optimizer.step() is skipped
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     const long long c = i >> 6;
     const float lr = clr[c] * lr_scale, wd = cwd[c];
+    const float q = TRUST ? ctr[c] : 1.f;
     float4 pv = reinterpret_cast<float4*>(p)[i];
     float4 gv = reinterpret_cast<const float4*>(g)[i];
     if (gscale) { gv.x *= gs; gv.y *= gs; gv.z *= gs; gv.w *= gs; }
@@ -115,6 +126,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     float d;
 #define GCA_SGD1(f)                                   \
     d = gv.f + wd * pv.f;                             \
+    if (TRUST) d = lars_scaled(q, d);                 \
     bv.f = first ? d : mom * bv.f + d;                \
     d = nesterov ? d + mom * bv.f : bv.f;             \
     pv.f = pv.f - lr * d;
@@ -123,6 +135,78 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     reinterpret_cast<float4*>(p)[i] = pv;
     reinterpret_cast<float4*>(buf)[i] = bv;
   }
+}
+
+// LARS (apex LARC(clip=False) around torch.optim.SGD): every tensor i of the arena scales its d = g + wd*p by
+//   q_i = tau * |w_i| / (|g_i| + wd_i * |w_i| + eps)      (1 where the tensor is not adapted, or |w_i| == 0, or |g_i| == 0)
+// Three launches, no atomics, every sum in a fixed order:
+//   lars_sqsum_kernel   one workgroup per JOB (a run of <= LARS_JOB_CHUNKS chunks inside ONE tensor; the host lays the job
+//                       table out once per arena): fp64 sums of w^2 and grad^2 (squares of fp32 values are exact in fp64;
+//                       padding elements are zero) -> two partials per job
+//   lars_trust_kernel   one workgroup per tensor: its jobs' partials folded in job order by one thread, the norms, q formed
+//                       in fp64 and rounded once, written per tensor and per chunk of the tensor
+//   sgd_kernel<true>    the SGD update with the per-chunk q
+// A set skip flag (grad_clip[2] != 0) ends all three at once: the last norms / trust record stays.
+constexpr int LARS_JOB_CHUNKS = 32;
+struct LarsJob { int param, chunk0, chunks; };                 // host table: int32 triples
+struct LarsParam { int job0, jobs, chunk0, chunks; };          // host table: int32 quadruples
+__global__ __launch_bounds__(256) void lars_sqsum_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                         const LarsJob* __restrict__ jobs, const float* __restrict__ gscale,
+                                                         double* __restrict__ part) {
+  if (gscale && gscale[2] != 0.f) return;
+  __shared__ double sh[4];
+  const LarsJob j = jobs[blockIdx.x];
+  const long long i0 = (long long)j.chunk0 * 64, i1 = i0 + (long long)j.chunks * 64;
+  double sw = 0.0, sg = 0.0;
+#pragma unroll 4
+  for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
+    const float4 a = reinterpret_cast<const float4*>(p)[i];
+    const float4 b = reinterpret_cast<const float4*>(g)[i];
+    sw += (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
+    sg += (double)b.x * b.x + (double)b.y * b.y + (double)b.z * b.z + (double)b.w * b.w;
+  }
+  sw = gca_block_sum256_d(sw, sh);
+  sg = gca_block_sum256_d(sg, sh);
+  if (threadIdx.x == 0) {
+    part[2 * (long long)blockIdx.x] = sw;
+    part[2 * (long long)blockIdx.x + 1] = sg;
+  }
+}
+__global__ __launch_bounds__(256) void lars_trust_kernel(const double* __restrict__ part, const LarsParam* __restrict__ params,
+                                                         const int* __restrict__ adapt, const float* __restrict__ cwd,
+                                                         double tau, double eps, const float* __restrict__ gscale,
+                                                         double* __restrict__ norms, float* __restrict__ trust,
+                                                         float* __restrict__ ctr) {
+  if (gscale && gscale[2] != 0.f) return;
+  __shared__ double shw[256], shg[256];
+  __shared__ float shq;
+  const LarsParam t = params[blockIdx.x];
+  double sw = 0.0, sg = 0.0;                                    // (thread 0's are the sums)
+  for (int base = 0; base < t.jobs; base += 256) {              // staged through LDS: the partials arrive in parallel,
+    const int k = base + threadIdx.x;                           // the fold stays one chain in job order
+    if (k < t.jobs) {
+      shw[threadIdx.x] = part[2 * (long long)(t.job0 + k)];
+      shg[threadIdx.x] = part[2 * (long long)(t.job0 + k) + 1];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = t.jobs - base < 256 ? t.jobs - base : 256;
+      for (int k2 = 0; k2 < m; ++k2) { sw += shw[k2]; sg += shg[k2]; }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double nw = sqrt(sw), ng = (gscale ? (double)gscale[1] : 1.0) * sqrt(sg);
+    float q = 1.f;
+    if (adapt[blockIdx.x] && nw > 0.0 && ng > 0.0) q = (float)(tau * nw / (ng + (double)cwd[t.chunk0] * nw + eps));
+    norms[2 * (long long)blockIdx.x] = nw;
+    norms[2 * (long long)blockIdx.x + 1] = ng;
+    trust[blockIdx.x] = q;
+    shq = q;
+  }
+  __syncthreads();
+  const float q = shq;
+  for (int c = threadIdx.x; c < t.chunks; c += 256) ctr[t.chunk0 + c] = q;
 }
 
 // torch.optim.Adam / AdamW (amsgrad=False, maximize=False) for step t = state[0] + 1, one pass over the arena:
@@ -331,8 +415,28 @@ int gca_sgd_step(float* p, const float* grad, float* mom_buf, int64_t n, const f
                  const float* chunk_wd, float lr_scale, float momentum, int nesterov, int first_step,
                  const float* grad_clip, void* stream) {
   if (!p || !grad || !mom_buf || !chunk_lr || !chunk_wd || n <= 0 || (n & 255)) return GCA_EINVAL;
-  hipLaunchKernelGGL(sgd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p, grad, mom_buf,
-                     (long long)(n / 4), chunk_lr, chunk_wd, lr_scale, momentum, nesterov, first_step, grad_clip);
+  hipLaunchKernelGGL(sgd_kernel<false>, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p, grad, mom_buf,
+                     (long long)(n / 4), chunk_lr, chunk_wd, lr_scale, momentum, nesterov, first_step, grad_clip,
+                     (const float*)nullptr);
+  return gca_launch_status();
+}
+int gca_lars_job_chunks(void) { return LARS_JOB_CHUNKS; }
+int gca_lars_step(float* p, const float* grad, float* mom_buf, int64_t n, const float* chunk_lr, const float* chunk_wd,
+                  const int32_t* jobs, int64_t n_jobs, const int32_t* params, const int32_t* adapt, int64_t n_params,
+                  double* partials, double* norms, float* trust, float* chunk_trust, float momentum, int nesterov,
+                  double trust_coef, double eps, const float* grad_clip, void* stream) {
+  if (!p || !grad || !mom_buf || !chunk_lr || !chunk_wd || !jobs || !params || !adapt || !partials || !norms || !trust ||
+      !chunk_trust || n <= 0 || (n & 255) || n / 256 > INT32_MAX || n_params <= 0 || n_jobs < n_params || n_jobs > n / 256 ||
+      !(trust_coef > 0.0) || !(eps >= 0.0) || !(momentum >= 0.f && momentum < 1.f))
+    return GCA_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(lars_sqsum_kernel, dim3((unsigned)n_jobs), dim3(256), 0, st, p, grad,
+                     reinterpret_cast<const LarsJob*>(jobs), grad_clip, partials);
+  hipLaunchKernelGGL(lars_trust_kernel, dim3((unsigned)n_params), dim3(256), 0, st, partials,
+                     reinterpret_cast<const LarsParam*>(params), adapt, chunk_wd, trust_coef, eps, grad_clip, norms, trust,
+                     chunk_trust);
+  hipLaunchKernelGGL(sgd_kernel<true>, dim3(ew_blocks(n / 4)), dim3(256), 0, st, p, grad, mom_buf, (long long)(n / 4),
+                     chunk_lr, chunk_wd, 1.f, momentum, nesterov, 0, grad_clip, chunk_trust);
   return gca_launch_status();
 }
 int gca_adam_step(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* chunk_lr,

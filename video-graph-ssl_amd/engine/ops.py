@@ -968,6 +968,58 @@ def adam_step(p, g, exp_avg, exp_avg_sq, chunk_lr, chunk_wd, beta1, beta2, eps, 
     H.call('gca_adam_advance', ptr(state), ptr(grad_clip), stream())
 
 
+def lars_job_tables(offsets, sizes, total, job_chunks=None):
+    """Host arithmetic of the LARS norm pass: cut every tensor of an arena (element offsets / sizes, each padded to whole
+    256-element chunks, `total` elements in all) into jobs of at most `job_chunks` chunks that never cross a tensor.
+    -> (jobs int32 (n_jobs, 3): tensor, first chunk, chunk count;  params int32 (n_params, 4): first job, job count, first
+    chunk, chunk count), as gca_lars_step reads them."""
+    J = int(job_chunks or H.lib.gca_lars_job_chunks())
+    jobs, params = [], []
+    for i, (o, s) in enumerate(zip(offsets, sizes)):
+        if o % 256 or s <= 0:
+            raise ValueError('tensor %d: offset %d, %d elements -- not an arena layout' % (i, o, s))
+        c0, nc = o // 256, (s + 255) // 256
+        if (c0 + nc) * 256 > total or (params and c0 < params[-1][2] + params[-1][3]):
+            raise ValueError('tensor %d lies outside the arena or over its predecessor' % i)
+        params.append((len(jobs), (nc + J - 1) // J, c0, nc))
+        jobs.extend((i, c, min(J, c0 + nc - c)) for c in range(c0, c0 + nc, J))
+    return torch.tensor(jobs, dtype=torch.int32).reshape(-1, 3), torch.tensor(params, dtype=torch.int32).reshape(-1, 4)
+
+
+class LarsPlan:
+    """Everything gca_lars_step needs beyond the SGD operands, allocated once per arena (nothing is sized or uploaded at step
+    time, so the step can be captured): the job tables, the fp64 partial sums, and the results -- `norms` (n_params, 2) fp64
+    (|w|, |g|), `trust` (n_params,) fp32 and its per-chunk copy.  `adapt` (n_params,) int32 is the caller's to fill."""
+
+    def __init__(self, offsets, sizes, total, device):
+        jobs, params = lars_job_tables(offsets, sizes, total)
+        self.total, self.n_jobs, self.n_params = int(total), jobs.shape[0], params.shape[0]
+        self.jobs, self.params = jobs.to(device), params.to(device)
+        self.adapt = torch.zeros(self.n_params, dtype=torch.int32, device=device)
+        self.partials = torch.zeros(self.n_jobs, 2, dtype=torch.float64, device=device)
+        self.norms = torch.zeros(self.n_params, 2, dtype=torch.float64, device=device)
+        self.trust = torch.ones(self.n_params, dtype=F32, device=device)
+        self.chunk_trust = torch.ones(self.total // 256, dtype=F32, device=device)
+
+
+def _f64ptr(t, like):
+    """Device pointer of one of a LarsPlan's fp64 records (ptr() is for the fp32 / integer operands)."""
+    if t.dtype is not torch.float64 or t.device != like.device or not t.is_contiguous():
+        raise TypeError('a contiguous fp64 tensor on %s expected' % like.device)
+    return t.data_ptr()
+
+
+def lars_step(p, g, buf, chunk_lr, chunk_wd, plan, momentum, nesterov, trust_coef, eps, grad_clip=None):
+    """One LARS step over the arena (three launches: per-job sums of squares, per-tensor trust ratio, update); `plan` is the
+    arena's LarsPlan, whose norms / trust it overwrites.  A set skip flag in `grad_clip` leaves all of it untouched."""
+    n = p.numel()
+    if plan.total != n or g.numel() != n or buf.numel() != n or chunk_lr.numel() != n // 256 or chunk_wd.numel() != n // 256:
+        raise ValueError('operands and LarsPlan describe arenas of different sizes')
+    H.call('gca_lars_step', ptr(p), ptr(g), ptr(buf), n, ptr(chunk_lr), ptr(chunk_wd), ptr(plan.jobs), plan.n_jobs,
+           ptr(plan.params), ptr(plan.adapt), plan.n_params, _f64ptr(plan.partials, p), _f64ptr(plan.norms, p), ptr(plan.trust),
+           ptr(plan.chunk_trust), float(momentum), int(bool(nesterov)), float(trust_coef), float(eps), ptr(grad_clip), stream())
+
+
 def grad_clip_coef(g, max_norm, out=None):
     """clip_grad_norm_ over the flat gradient arena -> device tensor (total_norm, clip coefficient, 0, 0)."""
     if out is None:

@@ -606,7 +606,7 @@ class ActionTrainer(_TrainerBase):
     tools/train_ds.py:97-125 (train) and :170-190 (validation) on the HIP engine.  Eager, single GPU, fp32 storage.
 
     Fine-tune (default): recording tape through the encoder and the fused class head (engine.layers.f_classifier), backward,
-    optional SOLVER.CLIP_GRADIENT, then make_optimizer(cfg, model)'s HipSGD / HipAdam over the whole model -- the
+    optional SOLVER.CLIP_GRADIENT, then make_optimizer(cfg, model)'s HipSGD / HipAdam / HipLARS over the whole model -- the
     reference's one-group-per-parameter rules.
 
     Linear probe (MODEL.LINEAR_PROBE): the encoder runs under model.train() on a non-recording tape, so nothing in it is
@@ -750,7 +750,7 @@ class ActionTrainer(_TrainerBase):
 
     def state_dict(self, epoch=0):
         """The reference's checkpoint format (tools/train_ds.py:153-158): epoch, state_dict (the reference's model keys),
-        optimizer (torch.optim.SGD's / Adam's wire format), best_pred.  In linear-probe mode the optimizer entry holds the class
+        optimizer (torch.optim.SGD's / Adam's wire format; LARS writes SGD's), best_pred.  In linear-probe mode the optimizer entry holds the class
         head's two groups only -- the probe's optimizer has no others."""
         return {'epoch': epoch, 'state_dict': self.model.state_dict(), 'optimizer': self.optimizer.state_dict(),
                 'best_pred': self.best_pred}

@@ -81,7 +81,7 @@ def get_defaults():
         'SOLVER': dict(OPTIMIZER_NAME='SGD', LR_SCHEDULER='poly', MAX_EPOCHS=50, START_EPOCH=0, BASE_LR=0.001,
                        BIAS_LR_FACTOR=2, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, WEIGHT_DECAY_BIAS=0, NESTEROV=False,
                        USE_TRICK=False, LR_STEP=20, CLIP_GRADIENT='none', NO_PARTIALBN=True, GAMMA=0.1,
-                       STEPS=(30, 60), WARMUP_FACTOR=1.0 / 3, WARMUP_ITERS=5, WARMUP_METHOD='linear'),
+                       STEPS=(30, 60), WARMUP_FACTOR=1.0 / 3, WARMUP_ITERS=5, WARMUP_METHOD='linear', LARS_TRUST_COEF=0.001, LARS_EPS=1e-8),
         'TEST': dict(BATCH_SIZE=128, WEIGHT=''),
         'APEX': dict(FLAG=False, OPT_LEVEL='O1', LOCAL_RANK=-1),
         'CHECKPOINT': dict(RESUME='none', CHECKNAME='video_model', CHECKPOINT_INTERVAL=20, NO_VAL=False,

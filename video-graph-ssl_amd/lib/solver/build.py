@@ -1,6 +1,7 @@
 """Optimiser / LR-schedule factories (reference: lib/solver/build.py:24-71).
 
-``make_optimizer(cfg, model)`` returns a HipSGD or a HipAdam (SOLVER.OPTIMIZER_NAME 'SGD' | 'Adam' | 'AdamW') whose
+``make_optimizer(cfg, model)`` returns a HipSGD, a HipAdam or a HipLARS (SOLVER.OPTIMIZER_NAME 'SGD' | 'Adam' | 'AdamW' |
+'LARS') whose
 ``param_groups`` mirror the reference's (one group PER PARAMETER; names containing "bias" get lr * BIAS_LR_FACTOR and
 WEIGHT_DECAY_BIAS), but whose ``step()`` is ONE multi-tensor kernel over the flat parameter arena instead of one
 launch per tensor."""
@@ -37,11 +38,17 @@ class _ArenaOptimizer(object):
         self._uploaded = None
         self._sync_tables()
 
+    def _table_key(self, g):
+        return (g['lr'], g['weight_decay'])
+
+    def _upload_tables(self):
+        self.chunk_lr.copy_(self.arena.chunk_table([g['lr'] for g in self.param_groups]), non_blocking=False)
+        self.chunk_wd.copy_(self.arena.chunk_table([g['weight_decay'] for g in self.param_groups]))
+
     def _sync_tables(self):
-        key = tuple((g['lr'], g['weight_decay']) for g in self.param_groups)
+        key = tuple(self._table_key(g) for g in self.param_groups)
         if key != self._uploaded:
-            self.chunk_lr.copy_(self.arena.chunk_table([g['lr'] for g in self.param_groups]), non_blocking=False)
-            self.chunk_wd.copy_(self.arena.chunk_table([g['weight_decay'] for g in self.param_groups]))
+            self._upload_tables()
             self._uploaded = key
 
     def zero_grad(self, set_to_none=False):
@@ -121,6 +128,80 @@ class HipSGD(_ArenaOptimizer):
         if len(moms) != 1 or len(nest) != 1:
             raise NotImplementedError('per-group momentum / nesterov settings are not supported by the fused SGD kernel')
         self.momentum, self.nesterov = moms.pop(), nest.pop()
+
+
+class HipLARS(_ArenaOptimizer):
+    """LARS -- apex LARC(clip=False) around torch.optim.SGD (dampening 0) -- on the arena: every tensor whose group has
+    `lars_adapt` set (default: p.ndim > 1, so biases and BatchNorm parameters take plain SGD) scales g + wd * w by its trust
+    ratio trust_coef * |w| / (|g| + wd * |w| + lars_eps) before momentum.  Three launches of gca_lars_step, no host sync.
+    `trust` (fp32, one per parameter) and `norms` (fp64 (n_params, 2): |w|, |g| with the clip coefficient in) are device
+    tensors that every applied step overwrites."""
+
+    def __init__(self, model, groups, momentum=0.9, nesterov=False, trust_coef=0.001, eps=1e-8):
+        self._bind(model, groups)
+        for g, p in zip(groups, self.arena.params):
+            g.setdefault('initial_lr', g['lr'])
+            g.setdefault('momentum', momentum)
+            g.setdefault('nesterov', nesterov)
+            g.setdefault('trust_coef', trust_coef)
+            g.setdefault('lars_eps', eps)
+            g.setdefault('lars_adapt', p.ndim > 1)
+        self.momentum, self.nesterov, self.trust_coef, self.eps = self._settings(groups)
+        a = self.arena
+        self.buf = torch.zeros_like(a.flat)
+        self.plan = ops.LarsPlan(a.offsets, a.sizes, a.total, a.flat.device)
+        self.trust, self.norms = self.plan.trust, self.plan.norms
+        self._make_tables()
+
+    def _settings(self, gs):
+        """The kernels take ONE (momentum, nesterov, trust_coef, lars_eps) setting: read it from the groups `gs`."""
+        sets = [set(kind(g[k]) for g in gs) for k, kind in (('momentum', float), ('nesterov', bool), ('trust_coef', float),
+                                                           ('lars_eps', float))]
+        if any(len(s_) != 1 for s_ in sets):
+            raise NotImplementedError('per-group momentum / nesterov / trust_coef / lars_eps settings are not supported by the '
+                                      'fused LARS kernels')
+        mom, nest, tau, eps = (s_.pop() for s_ in sets)
+        if not 0.0 <= mom < 1.0 or not tau > 0.0 or not eps >= 0.0:
+            raise ValueError('LARS needs 0 <= momentum < 1, trust_coef > 0, lars_eps >= 0 (got %r, %r, %r)' % (mom, tau, eps))
+        return mom, nest, tau, eps
+
+    def _table_key(self, g):
+        return (g['lr'], g['weight_decay'], bool(g['lars_adapt']))
+
+    def _upload_tables(self):
+        super(HipLARS, self)._upload_tables()
+        self.plan.adapt.copy_(torch.tensor([int(bool(g['lars_adapt'])) for g in self.param_groups], dtype=torch.int32))
+
+    def step(self, grad_clip=None):
+        """grad_clip: as for HipSGD.step -- the coefficient scales every gradient, inside the trust ratio too; a set skip flag
+        leaves parameters, momentum, `trust` and `norms` untouched."""
+        self._sync_tables()
+        ops.lars_step(self.arena.flat, self.arena.grad, self.buf, self.chunk_lr, self.chunk_wd, self.plan, self.momentum,
+                      self.nesterov, self.trust_coef, self.eps, grad_clip)
+
+    def state_dict(self):
+        """torch.optim.SGD's wire format, as HipSGD writes it (loads into a torch.optim.SGD over the same parameters); the
+        LARS settings ride in the param groups."""
+        state = {i: {'momentum_buffer': b} for i, b in self._per_param(self.buf).items()}
+        return {'state': state, 'param_groups': self._groups_out()}
+
+    def load_state_dict(self, sd):
+        """Its own state, or a plain SGD one (torch's or HipSGD's): groups without the LARS keys keep this optimizer's."""
+        if _state_keys(sd) & {'exp_avg', 'exp_avg_sq'}:
+            raise ValueError('HipLARS loads %s, and was handed the latter' % _FORMATS)
+        merged = self._groups_merged(sd)
+        settings = self._settings(merged)                    # refuses before anything is changed
+        a = self.arena
+        if 'momentum_buffer' in sd:                       # flat layout written by earlier builds of this package
+            self.buf.copy_(sd['momentum_buffer'])
+        else:
+            self.buf.zero_()
+            for i, (o, n) in enumerate(zip(a.offsets, a.sizes)):
+                st = sd['state'].get(i, sd['state'].get(str(i)))
+                if st is not None and st.get('momentum_buffer') is not None:
+                    self.buf[o:o + n].copy_(st['momentum_buffer'].reshape(-1))
+        self._groups_in(merged)
+        self.momentum, self.nesterov, self.trust_coef, self.eps = settings
 
 
 class HipAdam(_ArenaOptimizer):
@@ -203,7 +284,7 @@ def clip_value_of(cfg):
     return v
 
 
-OPTIMIZERS = ('SGD', 'Adam', 'AdamW')
+OPTIMIZERS = ('SGD', 'Adam', 'AdamW', 'LARS')
 
 
 def check_optimizer_name(cfg):
@@ -214,7 +295,8 @@ def check_optimizer_name(cfg):
 def make_optimizer(cfg, model, name_prefix=''):
     """The reference's make_optimizer over `model` (a sub-module whose parameters are the only ones trained: pass its
     place in the whole model as name_prefix -- the group names are then the whole model's).  SGD takes MOMENTUM / NESTEROV;
-    Adam / AdamW take the per-parameter lr / weight decay alone, with torch's default betas and eps (reference :57)."""
+    Adam / AdamW take the per-parameter lr / weight decay alone, with torch's default betas and eps (reference :57); LARS takes
+    MOMENTUM / NESTEROV, LARS_TRUST_COEF and LARS_EPS, and adapts every parameter of more than one dimension."""
     if cfg.SOLVER.USE_TRICK:
         raise NotImplementedError('SOLVER.USE_TRICK (TSN-style policies) is a downstream-only path')
     check_optimizer_name(cfg)
@@ -228,6 +310,9 @@ def make_optimizer(cfg, model, name_prefix=''):
         groups.append({'params': [value], 'lr': lr, 'weight_decay': wd, 'name': name_prefix + key})
     if cfg.SOLVER.OPTIMIZER_NAME == 'SGD':
         return HipSGD(model, groups, momentum=cfg.SOLVER.MOMENTUM, nesterov=cfg.SOLVER.NESTEROV)
+    if cfg.SOLVER.OPTIMIZER_NAME == 'LARS':
+        return HipLARS(model, groups, momentum=cfg.SOLVER.MOMENTUM, nesterov=cfg.SOLVER.NESTEROV,
+                       trust_coef=cfg.SOLVER.LARS_TRUST_COEF, eps=cfg.SOLVER.LARS_EPS)
     return HipAdam(model, groups, decoupled=cfg.SOLVER.OPTIMIZER_NAME == 'AdamW')
 
 
