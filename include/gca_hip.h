@@ -494,6 +494,31 @@ int gca_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, i
                        int32_t* first_hit, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Weighted k-NN classifier vote on the lists of gca_retrieval_topk (the evaluation of InstDisc / MoCo / SimSiam code bases on
+ * frozen features).  idx / dist (nq, k) as the search writes them: nearest first, tail slots idx = -1, dist = +inf;
+ * g_label (ng) int64; 1 <= kvote <= k <= 64; C classes.
+ *   valid slot j of query i: 0 <= idx[i,j] < ng, idx[i,j] != self_base + i when self_base >= 0 (leave-one-out: the queries
+ *                are rows self_base.. of the gallery), g_label[idx[i,j]] in [0, C), dist[i,j] not NaN
+ *   voters:      the first kvote valid slots in rank order
+ *   weight:      weighting 0: 1;  weighting 1: expf(-(dist * inv_T)), the product rounded once, the library expf -- for
+ *                cosine distances InstDisc's exp(sim / T) over the constant exp(1 / T): same ranking, no overflow
+ *   scores[i,c]: fp32 sum of the weights of class c's voters, added in rank order; 0 for a class without voters
+ *   order:       score descending, then class index ascending, over all C classes
+ *   pred[i]:     the first class of that order;  rank[i]: how many classes c != q_label[i] come before q_label[i]
+ *                (top-k' is correct iff rank < k'; rank == 0 iff pred == q_label).  No voter: pred = -1, rank = C.
+ * scores (nq, C) may be NULL (nothing of that size is then touched); rank may be NULL, and needs q_label (nq) int64.
+ * g_label is read and scores written only through range-checked indices: bad tables change results, never touch memory
+ * outside the buffers.  A q_label outside [0, C) leaves that row's rank unspecified and nothing else.  No atomics; outputs
+ * are bitwise the same from call to call.  No workspace.  Launches: the zero fill of scores when given, then one vote
+ * kernel (one wave per query).  tests/knn_ref.py is the numpy statement of all of the above.
+ * GCA_EINVAL (nothing launched, nothing written) for k outside [1, 64], kvote outside [1, k], C < 1, negative sizes,
+ * ng >= 2^31, nq >= 2^31, nq * C >= 2^31 with scores, another weighting, inv_T negative or not finite, rank without
+ * q_label, a NULL idx / dist / pred (or g_label with ng > 0).  nq == 0: returns 0, nothing launched. */
+int gca_knn_vote(const int32_t* idx, const float* dist, int64_t nq, int32_t k, int32_t kvote,
+                 const int64_t* g_label, int64_t ng, const int64_t* q_label, int64_t self_base, int64_t C,
+                 int32_t weighting, float inv_T, float* scores, int32_t* pred, int32_t* rank, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

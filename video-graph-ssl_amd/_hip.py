@@ -133,6 +133,8 @@ SIGNATURES = {
     'gca_retrieval_ws_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i32]),
     'gca_retrieval_topk': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                    c_i64, c_vp]),
+    'gca_knn_vote': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp,
+                             c_vp]),
     'gca_classifier_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_classifier_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'gca_classifier_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32,

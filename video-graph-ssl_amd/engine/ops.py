@@ -835,6 +835,54 @@ def retrieval_topk(q, g, k, metric='cosine', q_label=None, g_label=None, slabs=0
     return idx, dist, hit
 
 
+KNN_WEIGHTINGS = {'uniform': 0, 'exp': 1}
+
+
+def knn_vote(idx, dist, g_label, num_class, kvote=None, q_label=None, self_base=-1, weighting='exp', T=0.07, want_scores=False):
+    """Weighted k-NN vote on retrieval_topk's lists (gca_knn_vote; tests/knn_ref.py states the arithmetic): idx (nq, k) int32,
+    dist (nq, k) fp32, g_label (ng) int64 -> (pred (nq) int32, rank (nq) int32 or None, scores (nq, num_class) fp32 or None).
+    The first `kvote` (default k) valid slots of a row vote, each with weight 1 ('uniform') or exp(-dist / T) ('exp'); pred
+    is the class with the largest weight sum (ties: the lower class), -1 for a row without voters.  With q_label (nq) int64,
+    rank counts the other classes that come before the query's own (top-k' is correct iff rank < k').  self_base >= 0
+    drops slot idx == self_base + row (leave-one-out on a slice of the gallery).  ValueError for arguments the kernel entry
+    refuses; labels are not range-checked here (out-of-range gallery labels do not vote)."""
+    if weighting not in KNN_WEIGHTINGS:
+        raise ValueError('knn_vote: weighting must be one of %s (got %r)' % (sorted(KNN_WEIGHTINGS), weighting))
+    if idx.dim() != 2 or tuple(dist.shape) != tuple(idx.shape) or idx.dtype is not torch.int32 or dist.dtype is not F32:
+        raise ValueError('knn_vote: idx (nq, k) int32 and dist (nq, k) fp32 expected (got %s %s, %s %s)'
+                         % (tuple(idx.shape), idx.dtype, tuple(dist.shape), dist.dtype))
+    if g_label.dtype is not torch.int64 or g_label.dim() != 1:
+        raise ValueError('knn_vote: g_label is an int64 vector')
+    nq, k = idx.shape
+    if q_label is not None and (q_label.dtype is not torch.int64 or tuple(q_label.shape) != (nq,)):
+        raise ValueError('knn_vote: q_label is an int64 vector, one label per query')
+    ng, Cc, self_base = g_label.shape[0], int(num_class), int(self_base)
+    kvote = k if kvote is None else int(kvote)
+    if not 1 <= k <= 64 or not 1 <= kvote <= k:
+        raise ValueError('knn_vote: 1 <= kvote <= k <= 64 required (k=%d, kvote=%d)' % (k, kvote))
+    if Cc < 1 or Cc >= 2 ** 63 or ng >= 2 ** 31 or nq >= 2 ** 31 or not -2 ** 63 <= self_base < 2 ** 63:
+        raise ValueError('knn_vote: invalid sizes (nq=%d, ng=%d, num_class=%d)' % (nq, ng, Cc))
+    if want_scores and nq * Cc >= 2 ** 31:
+        raise ValueError('knn_vote: a (%d, %d) score block has 2^31 elements or more' % (nq, Cc))
+    T = float(T)
+    inv_T = 1.0 / T if T > 0 else float('nan')
+    if not (T > 0 and inv_T < 3.0e38):
+        raise ValueError('knn_vote: the temperature must be positive, 1 / T finite in fp32 (got %r)' % T)
+    idx, dist, g_label = idx.contiguous(), dist.contiguous(), g_label.contiguous()
+    ql = None if q_label is None else q_label.contiguous()
+    pi, pd, pg, pq = ptr(idx), ptr(dist), ptr(g_label), ptr(ql)          # (RuntimeError for host tensors)
+    dev = idx.device
+    pred = torch.empty((nq,), dtype=torch.int32, device=dev)
+    rank = torch.empty((nq,), dtype=torch.int32, device=dev) if ql is not None else None
+    scores = torch.empty((nq, Cc), dtype=F32, device=dev) if want_scores else None
+    rc = H.lib.gca_knn_vote(pi, pd, nq, k, kvote, pg, ng, pq, self_base, Cc, KNN_WEIGHTINGS[weighting], inv_T, ptr(scores),
+                            ptr(pred), ptr(rank), stream())
+    if rc == -1:
+        raise ValueError('knn_vote: gca_knn_vote refused its arguments')
+    H.check(rc, 'gca_knn_vote')
+    return pred, rank, scores
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

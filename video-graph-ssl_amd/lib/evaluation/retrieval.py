@@ -7,8 +7,9 @@ engine in eval mode and the search is ops.retrieval_topk (gca_retrieval_topk): f
 first-hit ranks, from which R@k for every k is a count.  Ties rank by gallery index (np.argsort(kind='stable')); the
 reference's default argsort leaves them undefined.
 
-Cropping / resizing of frames stays a host transform, as in the reference; the mean over views and the optional softmax
-are torch reductions over (B, views, feature_dim).
+Two inputs, as in lib/evaluation/classify.py: finished fp32 views made by a host transform (the reference's way), or
+decoded uint8 frames staged by engine.input.ActionInputStage(mode='test'), whose resize, crops and normalisation run on the
+device (gca_clip_views).  The mean over views and the optional softmax are torch reductions over (B, views, feature_dim).
 """
 import os
 import pickle
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from ...engine import ops
+from ...engine.input import ActionInputStage, StagedBatch
 from ...engine.tape import Tape, Var
 from ..modeling.visual_wrappers import VisualModelWrapper
 
@@ -50,18 +52,48 @@ def split_views(data, num_crops, video_length):
     return data.reshape((B, C, views, video_length) + tuple(data.shape[3:])).transpose(1, 2)
 
 
-def extract_feature_single(model, data, num_crops, video_length, softmax=False):
+def extract_feature_single(model, data, num_crops, video_length, softmax=False, views_buf=None):
     """One feature per video: a single eval-mode forward over all crops x clips views, then their mean
-    (tools/video_retrieval.py:101-115).  -> (B, feature_dim) on data's device."""
+    (tools/video_retrieval.py:101-115).  -> (B, feature_dim) on data's device.
+
+    data: (B, 3, clips * crops * T, H, W) finished views, or a StagedBatch of a test-mode engine.input.ActionInputStage
+    (decoded uint8 frames): gca_clip_views then cuts the (B * views, 3, T, H, W) block on the device, video-major, into
+    `views_buf` (a fp32 tensor of the stage's out_shape() that the caller keeps across batches; allocated here if None);
+    num_crops is the stage's own, as in classify.eval_video."""
     if model.training:
         raise RuntimeError('extract_feature_single needs the encoder in eval mode')
-    v = split_views(data, num_crops, video_length)
-    B, views = v.shape[:2]
-    x = v.reshape((B * views,) + tuple(v.shape[2:])).contiguous().float()
+    if isinstance(data, StagedBatch):
+        stage = data.stage
+        if not isinstance(stage, ActionInputStage) or stage.mode != 'test':
+            raise RuntimeError('extract_feature_single takes batches staged by a test-mode ActionInputStage')
+        if video_length != stage.T:
+            raise ValueError('video_length %d, but the batch was staged as clips of %d frames' % (video_length, stage.T))
+        if views_buf is None:
+            views_buf = torch.empty(stage.out_shape(), dtype=torch.float32, device=stage.device)
+        elif tuple(views_buf.shape) != tuple(stage.out_shape()) or views_buf.dtype is not torch.float32:
+            raise ValueError('views_buf must be a fp32 tensor of the stage\'s out_shape() %s' % (tuple(stage.out_shape()),))
+        B, views = stage.b, stage.views
+        x = stage.prepare(data, views_buf)
+    else:
+        v = split_views(data, num_crops, video_length)
+        B, views = v.shape[:2]
+        x = v.reshape((B * views,) + tuple(v.shape[2:])).contiguous().float()
     with torch.no_grad():
         out = model.fwd(Tape(False), Var(x, False)).t
         out = out.reshape(B, views, -1).mean(1)
         return torch.softmax(out, dim=-1) if softmax else out
+
+
+def batch_features(model, clips, num_crops, video_length, device, softmax=False, views_buf=None):
+    """extract_feature_single of one batch of a feature pass -> (features, views_buf): a tensor batch is moved to `device`;
+    a StagedBatch has its views cut into `views_buf`, which is (re)allocated when it does not fit the batch's stage and
+    handed back for the next batch."""
+    if not isinstance(clips, StagedBatch):
+        return extract_feature_single(model, clips.to(device), num_crops, video_length, softmax), views_buf
+    stage = clips.stage
+    if views_buf is None or tuple(views_buf.shape) != tuple(stage.out_shape()) or views_buf.device != stage.device:
+        views_buf = torch.empty(stage.out_shape(), dtype=torch.float32, device=stage.device)
+    return extract_feature_single(model, clips, num_crops, video_length, softmax, views_buf=views_buf), views_buf
 
 
 def feature_files(out_dir, split, features_file='features.pkl', classes_file='classes.pkl'):
@@ -71,11 +103,13 @@ def feature_files(out_dir, split, features_file='features.pkl', classes_file='cl
 def extract_features(model, batches, num_crops, video_length, out_dir, split, softmax=False, device=None,
                      features_file='features.pkl', classes_file='classes.pkl'):
     """Features of every (clips, target) batch -> ``{split}_features.pkl`` / ``{split}_classes.pkl`` in out_dir, pickled
-    numpy arrays as the reference writes them (:145-150).  -> (features, classes)."""
+    numpy arrays as the reference writes them (:145-150).  -> (features, classes).  `clips` may be a StagedBatch of a
+    test-mode ActionInputStage (see extract_feature_single); the views of every such batch are cut into one buffer."""
     device = torch.device('cuda') if device is None else device
-    feats, classes = [], []
+    feats, classes, buf = [], [], None
     for clips, target in batches:
-        feats.append(extract_feature_single(model, clips.to(device), num_crops, video_length, softmax).cpu())
+        f, buf = batch_features(model, clips, num_crops, video_length, device, softmax, buf)
+        feats.append(f.cpu())
         classes.append(torch.as_tensor(target).reshape(-1).cpu())
     feats, classes = torch.cat(feats, 0).numpy(), torch.cat(classes, 0).numpy()
     fpath, cpath = feature_files(out_dir, split, features_file, classes_file)
