@@ -152,6 +152,24 @@ int gca_conv_fwd(const gca_conv_geom* g, const void* x, const float* wpack, cons
 int64_t gca_conv_dgrad_ws_bytes(const gca_conv_geom* g);
 int gca_conv_dgrad(const gca_conv_geom* g, const void* dy, const float* wpack, const int32_t* table,
                    void* dx, int accumulate, void* ws, void* stream);
+/* A strided dgrad is one problem class per stride residue.  The classes write disjoint outputs, so when they run the same
+ * gather-kernel instantiation they go out in ONE launch (and one finishing launch); their split-K slabs then have to exist
+ * side by side: gca_conv_dgrad_ws_bytes_merged is the SUM over classes where gca_conv_dgrad_ws_bytes is the maximum.
+ * gca_conv_dgrad_ws is gca_conv_dgrad told how many bytes `ws` holds: with fewer than the sum (gca_conv_dgrad passes the
+ * maximum) the classes are launched one after another as before.  Same bits either way.  Inside the launch the classes go in
+ * by falling reduction length, so that the grid ends on its shortest workgroups.  GCA_DGRAD_MERGE=0 (read once) or
+ * gca_set_dgrad_merge(0) keep the per-class launches (A/B runs; 2 = merged with the classes in residue order, the A/B of
+ * the ordering); gca_set_dgrad_merge returns whether merging was on.
+ * gca_conv_dgrad_merged: 1 when gca_conv_dgrad_ws given `ws_bytes` of work space takes the single launch under the launch
+ * shape and setting in force, else 0 (tooling, tests).
+ * GCA_CLASS_BLOCK_BYTES bounds the by-value argument block of the merged launch (gca_conv_class_block_bytes: its size). */
+#define GCA_CLASS_BLOCK_BYTES 2048
+int gca_conv_dgrad_merged(const gca_conv_geom* g, int64_t ws_bytes);
+int64_t gca_conv_dgrad_ws_bytes_merged(const gca_conv_geom* g);
+int gca_conv_dgrad_ws(const gca_conv_geom* g, const void* dy, const float* wpack, const int32_t* table,
+                      void* dx, int accumulate, void* ws, int64_t ws_bytes, void* stream);
+int gca_set_dgrad_merge(int on);
+int64_t gca_conv_class_block_bytes(void);
 
 /* dw (+)= sum_{n,o} dy[n,k,o] * x[n,c,o*s-p+tap].  `table` from which=2.  Split-K partial slabs go
  * to `ws` (gca_conv_wgrad_ws_bytes) and are reduced deterministically. */

@@ -58,6 +58,11 @@ SIGNATURES = {
     'gca_conv_fwd': (c_i32, [_GP, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'gca_conv_dgrad_ws_bytes': (c_i64, [_GP]),
     'gca_conv_dgrad': (c_i32, [_GP, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'gca_conv_dgrad_ws_bytes_merged': (c_i64, [_GP]),
+    'gca_conv_dgrad_ws': (c_i32, [_GP, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    'gca_conv_dgrad_merged': (c_i32, [_GP, c_i64]),
+    'gca_set_dgrad_merge': (c_i32, [c_i32]),
+    'gca_conv_class_block_bytes': (c_i64, []),
     'gca_conv_wgrad_cfg': (c_i32, [_GP, c_vp]),
     'gca_conv_wgrad_ws_bytes': (c_i64, [_GP]),
     'gca_conv_wgrad': (c_i32, [_GP, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),

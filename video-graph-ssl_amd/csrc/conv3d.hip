@@ -711,16 +711,40 @@ __global__ __launch_bounds__(256) void conv_igemm_2phase_kernel(
   }
 }
 
+// Class of workgroup / finishing block `id` in a merged launch: ids past the last class's range do not exist and the unused
+// entries hold INT_MAX, so the count of range starts at or below `id` is the class (wave-uniform: scalar compares).
+__device__ __forceinline__ int class_of(const int* __restrict__ first, int id) {
+  int ci = 0;
+#pragma unroll
+  for (int i = 1; i < MAX_MERGED_CLASSES; ++i) ci += id >= first[i] ? 1 : 0;
+  return ci;
+}
+
+// All residue classes of a strided dgrad in ONE launch: the classes write disjoint outputs and share nothing, and one class
+// alone fills a fraction of the CUs.  Every class runs the same tile instantiation with its own parameters, packed weights,
+// gather rows and slabs; workgroup ids inside a class are remapped over the class's own block count.
+template <int TM, int BN, int FAST, bool VEC, int MATH, bool H = false>
+__global__ __launch_bounds__(256) void conv_igemm_classes_kernel(
+    const void* __restrict__ src, const float* __restrict__ apack, const int2* __restrict__ table, void* __restrict__ dst,
+    float* __restrict__ slab, const ClassBlock cb) {
+  __shared__ __attribute__((aligned(16))) float As_[lds_bufs(TM, VEC, MATH) * 32 * TM * lds_pitch(MATH)];
+  __shared__ __attribute__((aligned(16))) float Bs_[lds_bufs(TM, VEC, MATH) * BN * lds_pitch(MATH)];
+  __shared__ int taptab[64];
+  const int ci = class_of(cb.first_wg, (int)blockIdx.x);
+  const int first = cb.first_wg[ci], count = cb.first_wg[ci + 1] - first;
+  igemm_tile<TM, BN, FAST, VEC, MATH, H>(src, apack + cb.pack_off[ci], table + cb.table_off[ci], nullptr, dst, nullptr, nullptr,
+                                         slab + cb.slab_off[ci], cb.p[ci], gca_xcd_remap((int)blockIdx.x - first, count), As_, Bs_,
+                                         taptab);
+}
+
 // Split-K finishing pass, grid (channels, parts): sum the slabs in fixed order, add bias, (+=) store in
 // NCDHW (through the class's destination map), and emit the BN partial sums [K][parts].
 constexpr int FINISH_CHUNK = 1024;      // columns per finishing block: split-K grids are small, so many short blocks (4 columns per thread;
                                         // issuing the slab loads of all four columns together was measured: 9.1 vs 8.6 us per launch, not kept)
 template <typename T>
-__global__ __launch_bounds__(256) void conv_splitk_finish_kernel(
+__device__ __forceinline__ void splitk_finish_part(
     const float* __restrict__ slab, int splits, const float* __restrict__ bias, T* __restrict__ dst,
-    float* __restrict__ psum, float* __restrict__ psq, IgemmParams p) {
-  __shared__ double sh[4];
-  const int m = blockIdx.x, part = blockIdx.y, P = gridDim.y;
+    float* __restrict__ psum, float* __restrict__ psq, const IgemmParams& p, int m, int part, int P, double* sh) {
   const float b = bias ? bias[m] : 0.f;
   const long long lo = (long long)part * FINISH_CHUNK;
   long long hi = lo + FINISH_CHUNK; if (hi > p.Ntot) hi = p.Ntot;
@@ -754,6 +778,26 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(
     q = gca_block_sum256_d(q, sh);
     if (threadIdx.x == 0) { psum[(long long)m * P + part] = (float)s; psq[(long long)m * P + part] = (float)q; }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void conv_splitk_finish_kernel(
+    const float* __restrict__ slab, int splits, const float* __restrict__ bias, T* __restrict__ dst,
+    float* __restrict__ psum, float* __restrict__ psq, IgemmParams p) {
+  __shared__ double sh[4];
+  splitk_finish_part<T>(slab, splits, bias, dst, psum, psq, p, blockIdx.x, blockIdx.y, gridDim.y, sh);
+}
+
+// The finishing passes of all split classes of a merged dgrad launch in one: block y selects (class, part).  Per element
+// the fold is the one of the class's own finishing launch (slabs 0, 1, 2, ..., then the accumulate): same bits.
+template <typename T>
+__global__ __launch_bounds__(256) void conv_splitk_finish_classes_kernel(const float* __restrict__ slab, T* __restrict__ dst,
+                                                                         const ClassBlock cb) {
+  __shared__ double sh[4];
+  const int ci = class_of(cb.first_part, (int)blockIdx.y);
+  const int first = cb.first_part[ci];
+  splitk_finish_part<T>(slab + cb.slab_off[ci], cb.p[ci].splits, nullptr, dst, nullptr, nullptr, cb.p[ci], blockIdx.x,
+                        (int)blockIdx.y - first, cb.first_part[ci + 1] - first, sh);
 }
 
 // packed[m][k] (k contiguous, zero padded to [Mrows][Kpad]), k = (ch, t') over the class's tap grid:
@@ -1300,11 +1344,136 @@ int run_resolved_class(const gca_conv_geom* g, int which, const ConvLaunch& L, s
   return run_class(cf, fast_of(c.ntaps), src, apack, table, bias, dst, psum, psq, slab, p, st, leave_slabs);
 }
 
+inline int64_t class_slab_bytes(const IgemmCfg& cf, const IgemmParams& p) {
+  return cf.splits > 1 ? (int64_t)cf.splits * p.DK * p.Ntot * (int64_t)sizeof(float) : 0;
+}
+
+// ---- all classes of a strided dgrad in one launch -------------------------------------------
+int g_dgrad_merge = -1;     // -1: not read yet (GCA_DGRAD_MERGE)
+inline bool dgrad_merge_on() {
+  if (g_dgrad_merge < 0) {
+    const char* e = getenv("GCA_DGRAD_MERGE");
+    g_dgrad_merge = (e && !strcmp(e, "0")) ? 0 : (e && !strcmp(e, "2")) ? 2 : 1;     // (2: merged, classes in residue order)
+  }
+  return g_dgrad_merge != 0;
+}
+
+template <int TM, int BN, int FAST, bool VEC>
+void launch_classes_one(int math, bool h, dim3 grid, hipStream_t st, const float* src, const float* apack, const int2* table,
+                        float* dst, float* slab, const ClassBlock& cb) {
+  if (h)
+    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 3, true>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
+  else if (math == 1)
+    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 1>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
+  else if (math == 2)
+    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 2>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
+  else
+    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 0>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
+}
+
+template <int TM>
+void launch_classes_tm(const IgemmCfg& c, int fast, dim3 grid, hipStream_t st, const float* src, const float* apack,
+                       const int2* table, float* dst, float* slab, const ClassBlock& cb) {
+  if (c.bn == 256) launch_classes_one<TM, 256, 1, true>(c.math, c.h, grid, st, src, apack, table, dst, slab, cb);
+  else if (fast == 1) launch_classes_one<TM, 128, 1, false>(c.math, c.h, grid, st, src, apack, table, dst, slab, cb);
+  else launch_classes_one<TM, 128, 2, false>(c.math, c.h, grid, st, src, apack, table, dst, slab, cb);
+}
+
+// The classes with taps of dgrad plan `L` as ONE tile launch: the by-value class block and what the launch needs.
+struct MergedLaunch {
+  ClassBlock cb;
+  IgemmCfg cf;              // the tile instantiation all classes share (of the first class with taps)
+  int fast;
+  long long wg, parts;      // workgroups of the tile grid, y blocks of the finishing grid (0: no class splits)
+  int64_t slab_bytes;       // the slabs of all classes side by side
+};
+
+// -> true when the classes can share a launch: more than one and at most MAX_MERGED_CLASSES classes with taps, all on the
+// gather kernel with the same tile instantiation (rows, columns / float4 gathers, tap-mask kind, arithmetic, storage) and
+// single-phase.  Tap count, column count, tile counts and split factor are per-class run-time data.
+bool plan_merged(const ConvLaunch& L, int accumulate, MergedLaunch& m) {
+  m = MergedLaunch{};
+  ClassBlock& cb = m.cb;
+  int n = 0;
+  // Workgroups are dispatched in id order and a class's workgroups run for as long as its reduction (its tap count), so the
+  // classes go in by falling k-tiles per workgroup: the launch then ends on its shortest workgroups, not on its longest
+  // (the classes write disjoint outputs, so the order changes no bit).
+  std::vector<size_t> order;
+  for (size_t i = 0; i < L.cls.size(); ++i)
+    if (L.cls[i].ntaps > 0) order.push_back(i);
+  if (g_dgrad_merge != 2)
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return L.cf[a].kt_per_split > L.cf[b].kt_per_split; });
+  for (const size_t i : order) {
+    const ClassInfo& c = L.cls[i];
+    const IgemmCfg& cf = L.cf[i];
+    const int fast = fast_of(c.ntaps);
+    if (n == MAX_MERGED_CLASSES || cf.kernel != ConvKernel::Gather || cf.tail_bm > 0 || fast == 0) return false;
+    if (n == 0) { m.cf = cf; m.fast = fast; }
+    else if (cf.bm != m.cf.bm || cf.bn != m.cf.bn || fast != m.fast || cf.math != m.cf.math || cf.h != m.cf.h) return false;
+    IgemmParams p = L.p[i];                      // (as run_class sets a single-phase launch up)
+    p.accumulate = accumulate ? 1 : 0;
+    p.splits = cf.splits; p.kt_per_split = cf.kt_per_split;
+    p.P = stat_parts(cf, p.Ntot);
+    p.tilesM = (int)gca_ceil_div(p.DK, cf.bm);
+    p.tilesN = (int)gca_ceil_div(p.Ntot, cf.bn);
+    p.tileN_off = 0;
+    const long long nblk = (long long)p.tilesM * p.tilesN * cf.splits;
+    if (nblk <= 0 || (n > 0 && p.DK != cb.p[0].DK)) return false;
+    cb.p[n] = p;
+    cb.pack_off[n] = c.pack_off;
+    cb.table_off[n] = c.table_off;
+    cb.slab_off[n] = m.slab_bytes / (int64_t)sizeof(float);
+    cb.first_wg[n] = (int)m.wg;
+    cb.first_part[n] = (int)m.parts;
+    m.wg += nblk;
+    if (cf.splits > 1) m.parts += p.P;
+    m.slab_bytes += class_slab_bytes(cf, p);
+    if (m.wg > 0x7fffffffLL || m.parts > 65535) return false;
+    ++n;
+  }
+  if (n < 2) return false;
+  for (int i = n; i <= MAX_MERGED_CLASSES; ++i) { cb.first_wg[i] = 0x7fffffff; cb.first_part[i] = 0x7fffffff; }
+  cb.first_wg[n] = (int)m.wg;
+  cb.first_part[n] = (int)m.parts;
+  cb.n = n;
+  return true;
+}
+
+// One tile launch plus (where classes split the reduction) one finishing launch.
+int run_classes_merged(const MergedLaunch& m, const float* dy, const float* wpack, const int2* tab, float* dx, float* ws,
+                       hipStream_t st) {
+  const ClassBlock& cb = m.cb;
+  const dim3 grid((unsigned)m.wg);
+  switch (m.cf.bm / 32) {
+    case 1: launch_classes_tm<1>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
+    case 2: launch_classes_tm<2>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
+    case 3: launch_classes_tm<3>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
+    case 4: launch_classes_tm<4>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
+    default: launch_classes_tm<5>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
+  }
+  const int rc = gca_launch_status();
+  if (rc || m.parts == 0) return rc;
+  const dim3 fgrid((unsigned)cb.p[0].DK, (unsigned)m.parts);
+  if (m.cf.h)
+    hipLaunchKernelGGL(conv_splitk_finish_classes_kernel<_Float16>, fgrid, dim3(256), 0, st, ws, reinterpret_cast<_Float16*>(dx), cb);
+  else
+    hipLaunchKernelGGL(conv_splitk_finish_classes_kernel<float>, fgrid, dim3(256), 0, st, ws, dx, cb);
+  return gca_launch_status();
+}
+
 int64_t ws_bytes_for(const gca_conv_geom* g, int which) {
   const ConvLaunch L = resolve_launch(g, which);
   int64_t need = 0;
   for (size_t i = 0; i < L.cls.size(); ++i)
     if (L.cf[i].splits > 1) need = std::max<int64_t>(need, (int64_t)L.cf[i].splits * L.p[i].DK * L.p[i].Ntot * (int64_t)sizeof(float));
+  return need;
+}
+
+// the slabs of all classes side by side (what the merged dgrad launch needs); never less than ws_bytes_for
+int64_t ws_bytes_merged_for(const gca_conv_geom* g, int which) {
+  const ConvLaunch L = resolve_launch(g, which);
+  int64_t need = 0;
+  for (size_t i = 0; i < L.cls.size(); ++i) need += class_slab_bytes(L.cf[i], L.p[i]);
   return need;
 }
 
@@ -1561,8 +1730,23 @@ int gca_conv_fwd_xf(const gca_conv_geom* g, const void* x_, const float* in_scal
                             reinterpret_cast<float*>(ws), 0, (hipStream_t)stream, false, in_scale, in_shift);
 }
 
-int gca_conv_dgrad(const gca_conv_geom* g, const void* dy_, const float* wpack, const int32_t* table,
-                   void* dx_, int accumulate, void* ws, void* stream) {
+int64_t gca_conv_dgrad_ws_bytes_merged(const gca_conv_geom* g) { return geom_ok(g) ? ws_bytes_merged_for(g, 1) : GCA_EINVAL; }
+int64_t gca_conv_class_block_bytes(void) { return (int64_t)sizeof(ClassBlock); }
+int gca_conv_dgrad_merged(const gca_conv_geom* g, int64_t ws_bytes) {
+  if (!geom_ok(g)) return GCA_EINVAL;
+  const ConvLaunch L = resolve_launch(g, 1);
+  MergedLaunch m;
+  return L.cls.size() > 1 && dgrad_merge_on() && plan_merged(L, 0, m) && ws_bytes >= m.slab_bytes;
+}
+
+int gca_set_dgrad_merge(int on) {
+  const int was = dgrad_merge_on() ? 1 : 0;
+  g_dgrad_merge = on == 2 ? 2 : (on ? 1 : 0);
+  return was;
+}
+
+int gca_conv_dgrad_ws(const gca_conv_geom* g, const void* dy_, const float* wpack, const int32_t* table,
+                      void* dx_, int accumulate, void* ws, int64_t ws_bytes, void* stream) {
   const float* dy = reinterpret_cast<const float*>(dy_);
   float* dx = reinterpret_cast<float*>(dx_);
   if (!geom_ok(g) || !dy || !wpack || !table || !dx) return GCA_EINVAL;
@@ -1580,6 +1764,9 @@ int gca_conv_dgrad(const gca_conv_geom* g, const void* dy_, const float* wpack, 
                        g->act_f16 ? (int)(n & 1) : 0);
   }
   const int2* tab = reinterpret_cast<const int2*>(table);
+  MergedLaunch m;          // strided: every class with taps in one launch where they allow it and `ws` holds all their slabs
+  if (L.cls.size() > 1 && dgrad_merge_on() && plan_merged(L, accumulate, m) && (m.slab_bytes == 0 || (ws && ws_bytes >= m.slab_bytes)))
+    return run_classes_merged(m, dy, wpack, tab, dx, reinterpret_cast<float*>(ws), st);
   for (size_t i = 0; i < L.cls.size(); ++i) {
     const ClassInfo& c = L.cls[i];
     if (c.ntaps == 0) continue;
@@ -1588,6 +1775,12 @@ int gca_conv_dgrad(const gca_conv_geom* g, const void* dy_, const float* wpack, 
     if (rc) return rc;
   }
   return GCA_OK;
+}
+
+int gca_conv_dgrad(const gca_conv_geom* g, const void* dy, const float* wpack, const int32_t* table,
+                   void* dx, int accumulate, void* ws, void* stream) {
+  // (this entry does not know the size of `ws`: the caller sized it with gca_conv_dgrad_ws_bytes, the maximum over classes)
+  return gca_conv_dgrad_ws(g, dy, wpack, table, dx, accumulate, ws, geom_ok(g) && ws ? ws_bytes_for(g, 1) : 0, stream);
 }
 
 }  // extern "C"

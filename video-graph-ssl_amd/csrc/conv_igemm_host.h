@@ -31,6 +31,22 @@ struct IgemmParams {
   unsigned slab_bytes;     // extent of one fp32 split-K slab [DK][Ntot]
 };
 
+// All residue classes of a strided dgrad in ONE launch (conv_igemm_classes_kernel / conv_splitk_finish_classes_kernel):
+// passed BY VALUE as a kernel argument, so nothing is uploaded per call and the launch stays capturable.  Class i owns
+// workgroups [first_wg[i], first_wg[i+1]) of the tile grid and blocks [first_part[i], first_part[i+1]) of the finishing grid's
+// y axis; entries past the last class hold INT_MAX, so a workgroup finds its class with seven wave-uniform compares.
+constexpr int MAX_MERGED_CLASSES = 8;
+struct ClassBlock {
+  IgemmParams p[MAX_MERGED_CLASSES];
+  long long pack_off[MAX_MERGED_CLASSES];    // floats inside the packed buffer
+  long long table_off[MAX_MERGED_CLASSES];   // int2 units inside the table buffer
+  long long slab_off[MAX_MERGED_CLASSES];    // floats inside the work space: the classes' slabs exist side by side
+  int first_wg[MAX_MERGED_CLASSES + 1];
+  int first_part[MAX_MERGED_CLASSES + 1];
+  int n, pad_;
+};
+static_assert(sizeof(ClassBlock) <= GCA_CLASS_BLOCK_BYTES, "gca_hip.h: GCA_CLASS_BLOCK_BYTES too small");
+
 // ---- host side: problem classes ---------------------------------------------------------------
 struct ClassInfo {
   int na, nb, nc, ntaps;        // tap grid of the class

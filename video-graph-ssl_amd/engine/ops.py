@@ -178,6 +178,9 @@ class ConvPlan:
         self.wgrad_ws = H.lib.gca_conv_wgrad_ws_bytes(self.gp)
         self.fwd_ws = H.lib.gca_conv_fwd_ws_bytes(self.gp)
         self.dgrad_ws = H.lib.gca_conv_dgrad_ws_bytes(self.gp) if self.g.x_batch_stride == 0 else 0
+        # a strided dgrad runs its residue classes in one launch when their split-K slabs fit side by side (the sum over
+        # classes; dgrad_ws is the maximum)
+        self.dgrad_ws_merged = H.lib.gca_conv_dgrad_ws_bytes_merged(self.gp) if self.g.x_batch_stride == 0 else 0
 
     def table(self, which):
         t = self._tables.get(which)
@@ -375,10 +378,19 @@ def conv_fwd_xf(plan, y_in, scale, shift, wpack, stats=False):
     return (y, (ss, sq)) if stats else y
 
 
-def _conv_dgrad_launch(plan, dy, wpack_t, dx, accumulate):
-    ws = WS.get(plan.dgrad_ws, dy.device) if plan.dgrad_ws else None
-    H.call('gca_conv_dgrad', plan.gp, _act(plan, dy), ptr(wpack_t), ptr(plan.table(1)), _act(plan, dx), int(accumulate), ptr(ws),
-           stream())
+def set_dgrad_merge(on):
+    """Strided dgrads as one launch over all stride-residue classes (default; GCA_DGRAD_MERGE=0 in the environment turns it
+    off) or one launch per class.  Same bits either way (A/B runs, tests).  -> the previous setting."""
+    return bool(H.lib.gca_set_dgrad_merge(int(bool(on))))
+
+
+def _conv_dgrad_launch(plan, dy, wpack_t, dx, accumulate, ws_bytes=None):
+    """ws_bytes: scratch handed to the library (default: room for the merged launch of a strided dgrad; with only
+    plan.dgrad_ws the library launches the classes one after another)."""
+    need = max(plan.dgrad_ws, plan.dgrad_ws_merged) if ws_bytes is None else ws_bytes
+    ws = WS.get(need, dy.device) if need else None
+    H.call('gca_conv_dgrad_ws', plan.gp, _act(plan, dy), ptr(wpack_t), ptr(plan.table(1)), _act(plan, dx), int(accumulate), ptr(ws),
+           need, stream())
 
 
 def conv_dgrad(plan, dy, wpack_t, dx=None, accumulate=False, w_raw=None):
