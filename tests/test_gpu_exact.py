@@ -126,7 +126,8 @@ def test_gather_kernels_every_launch_configuration_bit_exact(ops, mode, name):
         tilesN = -(-Ntot // 128)
         if tilesN < 2 or (which == 1 and (tuple(c.s) != (1, 1, 1) or not full)):
             continue
-        for bm, tail in ((64, 1), (160, 2), (96, 1)):
+        # the seven (tall, short) pairs that run as one launch, then two that take one launch per phase
+        for bm, tail in ((64, 1), (96, 1), (96, 2), (128, 1), (128, 2), (160, 1), (160, 2), (160, 3), (128, 3)):
             for mc in sorted({1, tilesN // 2, tilesN - 1}):
                 if mc < 1:
                     continue

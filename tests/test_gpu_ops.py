@@ -12,6 +12,8 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
 CONVS = ['stem_s', 'stem_t', 's3d_t_s2', 'c1x3x3', 'c1x3x3_s2', 'c3x1x1', 'c3x1x1_s2', 'c1x1x1_s2', 'c1x1x1',
          'c3x3x3', 'c3x3x3_s2', 'c7x7x7']
+# (tile rows, short tile rows / 32) of the two-phase launches: the seven pairs that run as one launch, then two that take two
+TWO_PHASE_PAIRS = ((64, 1), (96, 1), (96, 2), (128, 1), (128, 2), (160, 1), (160, 2), (160, 3), (128, 3))
 
 
 @pytest.fixture(scope='module')
@@ -81,10 +83,14 @@ def test_conv_random_vs_aten(ops, ctol, shape, K, k, s, p):
     ((2, 24, 6, 8, 8), 70, (3, 1, 1), (2, 1, 1), (1, 0, 0)),        # ... with temporal stride (dgrad classes)
     ((2, 20, 3, 12, 12), 100, (1, 3, 3), (1, 2, 2), (0, 1, 1)),     # spatial window, strided (4 dgrad classes)
     ((2, 33, 1, 1, 1), 170, (1, 1, 1), (1, 1, 1), (0, 0, 0)),       # Linear
+    ((2, 6, 3, 10, 10), 40, (1, 7, 7), (1, 1, 1), (0, 3, 3)),       # 49 taps: the 62-tap mask kind in both passes, 5 column tiles
+    ((1, 4, 5, 6, 6), 40, (5, 5, 5), (1, 1, 1), (2, 2, 2)),         # 125 taps: window tests per element, 2 column tiles
 ])
 def test_conv_every_launch_configuration(ops, ctol, shape, K, k, s, p):
     """Force every tile height (32..160), the 256-column float4 variant, and split-K factors through the
-    tune_* fields: all must give the same convolution (the autotuner may pick any of them)."""
+    tune_* fields: all must give the same convolution (the autotuner may pick any of them).  Plain row codes keep both
+    passes on the gather kernels; the two-phase list holds every (tall, short) pair the single-launch kernel is built for
+    and two pairs that take one launch per phase (as does every pair on the 125-tap shape)."""
     torch.manual_seed(0)
     x = torch.randn(shape)
     w = torch.randn((K, shape[1]) + tuple(k)) * 0.1
@@ -118,7 +124,7 @@ def test_conv_every_launch_configuration(ops, ctol, shape, K, k, s, p):
         tilesN = -(-Ntot // 128)
         if tilesN < 2 or (which == 1 and tuple(s) != (1, 1, 1)):
             continue
-        for bm, tail in ((64, 1), (160, 2), (96, 1)):
+        for bm, tail in TWO_PHASE_PAIRS:
             for mc in sorted({1, tilesN // 2, tilesN - 1}):
                 if mc < 1:
                     continue
@@ -143,7 +149,8 @@ def test_conv_every_launch_configuration(ops, ctol, shape, K, k, s, p):
             dw = torch.zeros_like(wd)
             ops.conv_wgrad(plan, xd, dyd, dw, accumulate=True)
             assert rel_err(dw, wr.grad) < ctol, (idx, sp, plan.cfg(2))
-    assert len(seen_w) >= 6
+    # (past 31 taps the wgrad kernel is built in four shapes per tap-mask kind: WGRAD_SHAPES' `fasts`)
+    assert len(seen_w) >= (6 if k[0] * k[1] * k[2] <= 31 else 4)
 
 
 def _boxes(bn, q, m, k):

@@ -477,6 +477,57 @@ def test_conv_fwd_slabs_refuses_non_split_launches_before_launching(pkg):
         H.lib.gca_set_conv_math(default)
 
 
+# (tile rows, short tile rows / 32) of forced two-phase launches: the seven pairs conv_igemm_2phase_kernel is built for, then
+# two pairs that take one launch per phase
+TWO_PHASE_PAIRS = ((64, 1), (96, 1), (96, 2), (128, 1), (128, 2), (160, 1), (160, 2), (160, 3), (128, 3))
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='dummy operand pointers: only meaningful where nothing can run')
+def test_conv_gather_dispatch_reaches_a_launch_for_every_forced_tile(pkg):
+    """The forward / dgrad tile dispatcher, checked where nothing can run: for every forced gather configuration -- rows
+    32..160, without and with the 256-column bit, splits 1 and 3, arithmetic modes 0 / 1 / 2 and fp16 storage, and the
+    two-phase pairs -- on a <= 31-tap, a 49-tap and a 125-tap geometry, gca_conv_fwd and gca_conv_dgrad_ws (merged and per
+    class) find an instantiation and attempt the launch: GCA_ELAUNCH (-2) on dummy pointers and a null stream, never the
+    refusal GCA_EINVAL (-1) a tile outside the built set would get."""
+    H = pkg._hip
+    ops = pkg.engine.ops
+    cpu = torch.device('cpu')
+    geoms = (((2, 24, 6, 8, 8), 70, (3, 1, 1), (2, 1, 1), (1, 0, 0)),     # 3 taps, float4 gathers possible, two dgrad classes
+             ((2, 6, 3, 10, 10), 40, (1, 7, 7), (1, 1, 1), (0, 3, 3)),    # 49 taps: the 62-tap mask kind
+             ((1, 4, 5, 6, 6), 40, (5, 5, 5), (1, 1, 1), (2, 2, 2)))      # 125 taps: window tests per element
+    dummy = 1 << 20
+    default, merge = H.lib.gca_get_conv_math(), H.lib.gca_set_dgrad_merge(1)
+
+    def attempt(plan, code, sp, tail, tag):
+        g = plan.g
+        g.tune_fwd_bm = g.tune_dgrad_bm = code
+        g.tune_fwd_splits = g.tune_dgrad_splits = sp
+        g.tune_fwd_tail = g.tune_dgrad_tail = tail
+        for which in (0, 1):
+            assert plan.kernel(which) == 'gather' and plan.cfg(which)[0] == code & 1023, (tag, which, plan.cfg(which))
+        assert H.lib.gca_conv_fwd(plan.gp, dummy, dummy, dummy, None, dummy, dummy, dummy, dummy, None) == -2, ('fwd',) + tag
+        assert H.lib.gca_conv_dgrad_ws(plan.gp, dummy, dummy, dummy, dummy, 0, dummy, 1 << 40, None) == -2, ('dgrad',) + tag
+
+    try:
+        for shape, K, k, s, p in geoms:
+            for math, f16 in ((0, False), (1, False), (2, False), (2, True)):
+                assert H.lib.gca_set_conv_math(math) == 0
+                plan = ops.ConvPlan(*shape, K, k, s, p, cpu, act_f16=f16)
+                strided = tuple(s) != (1, 1, 1)
+                for merged in ((1, 0) if strided else (1,)):
+                    H.lib.gca_set_dgrad_merge(merged)
+                    assert H.lib.gca_conv_dgrad_merged(plan.gp, 1 << 40) == (1 if strided and merged else 0)
+                    for rows in (32, 64, 96, 128, 160):
+                        for wide in (0, 1024):
+                            for sp in (1, 3):
+                                attempt(plan, rows | wide, sp, 0, (shape, math, f16, merged, rows | wide, sp))
+                    for bm, tail in TWO_PHASE_PAIRS:
+                        attempt(plan, bm, 1, tail | (1 << 8), (shape, math, f16, merged, bm, tail))
+    finally:
+        H.lib.gca_set_conv_math(default)
+        H.lib.gca_set_dgrad_merge(merge)
+
+
 def test_bench_stdout_carries_only_the_result_line():
     """bench.py's contract is ONE JSON line on stdout.  RCCL writes a version banner to file descriptor 1 from native code when
     the first communicator is created (seen on the GPU box), so bench.py points descriptor 1 at stderr and emits the result

@@ -37,7 +37,6 @@ using namespace gca_conv;
 
 namespace {
 
-
 // ---------------------------------------------------------------------------------------------
 // 256 threads = 4 waves side by side along N: every wave owns all BM = 32*TM rows of the block tile and
 // BN/4 of its columns (TN = BN/128 MFMA tiles wide).  LDS tiles are stored [row][k] with an 80-byte row
@@ -875,7 +874,6 @@ struct IgemmCfg {
                          // multiply in bf16x3 (exact for fp16 operands); the halo kernels multiply on the f16 MFMA (math 3)
 };
 
-
 // Split of a reduction of nk steps over `tiles` output tiles of an M x Ntot problem: forced (> 0), or when the tile grid cannot
 // occupy the CUs and the slabs stay small.  -> splits; `per` = steps per split.
 inline int split_k(long long tiles, int nk, long long M, long long Ntot, int force, int& per) {
@@ -1152,32 +1150,54 @@ inline long long halo_tiles_n(const gca_conv_geom* g, const ClassInfo& c, const 
   return (long long)g->N * cdiv(c.q[0], cf.bd) * cdiv(c.q[1], cf.bh) * cdiv(c.q[2], cf.bw);
 }
 
-template <int TM, int BN, int FAST, bool VEC>
-void launch_one(int math, dim3 grid, hipStream_t st, const float* src, const float* apack, const int2* table, const float* bias,
-                float* dst, float* psum, float* psq, float* slab, const IgemmParams& p, bool h = false) {
-  if (h)
-    hipLaunchKernelGGL((conv_igemm_kernel<TM, BN, FAST, VEC, 3, true>), grid, dim3(256), 0, st, src, apack, table, bias,
-                       dst, psum, psq, slab, p);
-  else if (math == 1)
-    hipLaunchKernelGGL((conv_igemm_kernel<TM, BN, FAST, VEC, 1>), grid, dim3(256), 0, st, src, apack, table, bias,
-                       dst, psum, psq, slab, p);
-  else if (math == 2)
-    hipLaunchKernelGGL((conv_igemm_kernel<TM, BN, FAST, VEC, 2>), grid, dim3(256), 0, st, src, apack, table, bias,
-                       dst, psum, psq, slab, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_kernel<TM, BN, FAST, VEC, 0>), grid, dim3(256), 0, st, src, apack, table, bias,
-                       dst, psum, psq, slab, p);
+// ---- gather-tile instantiations ------------------------------------------------------------
+// Which igemm_tile<TM, BN, FAST, VEC, MATH, H> a gather launch runs, as a value.  The template axes are coupled, and the
+// coupling is written here and nowhere else:
+//   256 columns  <=>  VEC (float4 gathers); the class builder grants them to <= 31-tap classes only, so FAST is 1
+//   fp16 storage  =>  MATH 3 with H (the f16 MFMA on halves widened on load); MATH 3 exists in no other form
+struct TileInst {
+  int tm;        // rows / 32
+  int kind;      // 128 columns with tap-mask kind FAST = 0, 1, 2 (fast_of); 3 = 256 columns
+  int math;      // 0 fp32 MFMA, 1 bf16x3, 2 bf16x6, 3 fp16 storage
+  bool operator==(const TileInst& o) const { return tm == o.tm && kind == o.kind && math == o.math; }
+};
+inline TileInst tile_inst(const IgemmCfg& c, int fast, int rows) {
+  return TileInst{rows / 32, c.bn == 256 ? 3 : fast, c.h ? 3 : (c.math == 1 || c.math == 2 ? c.math : 0)};
+}
+template <int TM_, int KIND, int MATH_>       // ... and as compile-time parameters: what the dispatcher hands to a launcher
+struct Tile {
+  static constexpr int TM = TM_, BN = KIND == 3 ? 256 : 128, FAST = KIND == 3 ? 1 : KIND, MATH = MATH_;
+  static constexpr bool VEC = KIND == 3, H = MATH_ == 3;
+};
+
+// The part of that space each kernel family is built for: bit `kind`, and TILES_HALF for fp16 storage.
+constexpr unsigned TILES_HALF = 16;
+constexpr unsigned SINGLE_TILES = 15 | TILES_HALF;     // conv_igemm_kernel: everything
+constexpr unsigned MERGED_TILES = 14 | TILES_HALF;     // conv_igemm_classes_kernel: no FAST 0 (window tests per element)
+constexpr unsigned TWO_PHASE_TILES = 6;                // conv_igemm_2phase_kernel: 128 columns, mask kinds 1 / 2, fp32 storage, and
+constexpr int TWO_PHASE_ROWS[][2] = {{2, 1}, {3, 1}, {3, 2}, {4, 1}, {4, 2}, {5, 1}, {5, 2}};      // these (tall, short) rows / 32
+constexpr bool two_phase_rows(int tall, int tail) {
+  for (const auto& r : TWO_PHASE_ROWS) if (r[0] == tall && r[1] == tail) return true;
+  return false;
 }
 
-template <int TM>
-void launch_tm(const IgemmCfg& c, int fast, dim3 grid, hipStream_t st, const float* src, const float* apack,
-               const int2* table, const float* bias, float* dst, float* psum, float* psq, float* slab,
-               const IgemmParams& p) {
-  if (c.bn == 256) launch_one<TM, 256, 1, true>(c.math, grid, st, src, apack, table, bias, dst, psum, psq, slab, p, c.h);
-  else if (fast == 1) launch_one<TM, 128, 1, false>(c.math, grid, st, src, apack, table, bias, dst, psum, psq, slab, p, c.h);
-  else if (fast == 2) launch_one<TM, 128, 2, false>(c.math, grid, st, src, apack, table, bias, dst, psum, psq, slab, p, c.h);
-  else launch_one<TM, 128, 0, false>(c.math, grid, st, src, apack, table, bias, dst, psum, psq, slab, p, c.h);
+// f(Tile<...>{}) for tile `t` where family SET is built for it -> f's result; else TILE_NOT_BUILT, and nothing was launched.
+// I runs over the whole space (5 heights x 4 arithmetics x 4 kinds); only SET's part of it instantiates f.
+constexpr int TILE_NOT_BUILT = 1;
+template <unsigned SET, class F, int... I>
+int with_tile(const TileInst& t, F&& f, std::integer_sequence<int, I...>) {
+  int rc = TILE_NOT_BUILT;
+  auto at = [&](auto TM, auto MATH, auto KIND) {
+    if constexpr ((SET >> KIND() & 1) != 0 && (MATH() != 3 || (SET & TILES_HALF) != 0))
+      if (t.tm == TM() && t.math == MATH() && t.kind == KIND()) rc = f(Tile<TM(), KIND(), MATH()>{});
+  };
+  (at(std::integral_constant<int, I / 16 + 1>{}, std::integral_constant<int, I / 4 % 4>{}, std::integral_constant<int, I % 4>{}), ...);
+  return rc;
 }
+template <unsigned SET, class F>
+int with_tile(const TileInst& t, F&& f) { return with_tile<SET>(t, f, std::make_integer_sequence<int, 80>()); }
+template <unsigned SET>
+bool tile_built(const TileInst& t) { return with_tile<SET>(t, [](auto) { return 0; }) != TILE_NOT_BUILT; }
 
 inline int stat_parts(const IgemmCfg& c, long long Ntot, long long halo_tiles = 0) {
   if (c.splits > 1) return (int)gca_ceil_div(Ntot, FINISH_CHUNK);
@@ -1185,86 +1205,80 @@ inline int stat_parts(const IgemmCfg& c, long long Ntot, long long halo_tiles = 
   return (int)gca_ceil_div(Ntot, c.bn);
 }
 
-// the split-K finishing pass of a class (p.P parts)
-int finish_slabs(const IgemmCfg& c, const float* slab, const float* bias, float* dst, float* psum, float* psq, const IgemmParams& p,
-                 hipStream_t st) {
+// the split-K finishing pass of a class (p.P parts): bias, (+=) store and the statistics the tile kernel left out
+int finish_slabs(const IgemmCfg& c, const ConvOperands& o, const IgemmParams& p) {
   const dim3 grid((unsigned)p.DK, (unsigned)p.P);
   if (c.h)
-    hipLaunchKernelGGL(conv_splitk_finish_kernel<_Float16>, grid, dim3(256), 0, st, slab, c.splits, bias,
-                       reinterpret_cast<_Float16*>(dst), psum, psq, p);
+    hipLaunchKernelGGL(conv_splitk_finish_kernel<_Float16>, grid, dim3(256), 0, o.st, o.slab, c.splits, o.bias,
+                       reinterpret_cast<_Float16*>(o.dst), o.psum, o.psq, p);
   else
-    hipLaunchKernelGGL(conv_splitk_finish_kernel<float>, grid, dim3(256), 0, st, slab, c.splits, bias, dst, psum, psq, p);
+    hipLaunchKernelGGL(conv_splitk_finish_kernel<float>, grid, dim3(256), 0, o.st, o.slab, c.splits, o.bias, o.dst, o.psum, o.psq, p);
   return gca_launch_status();
 }
 
-int launch_tiles(int bm, const IgemmCfg& c, int fast, dim3 grid, hipStream_t st, const float* src, const float* apack,
-                 const int2* table, const float* bias, float* dst, float* ps, float* pq, float* slab, const IgemmParams& p) {
-  switch (bm / 32) {
-    case 1: launch_tm<1>(c, fast, grid, st, src, apack, table, bias, dst, ps, pq, slab, p); break;
-    case 2: launch_tm<2>(c, fast, grid, st, src, apack, table, bias, dst, ps, pq, slab, p); break;
-    case 3: launch_tm<3>(c, fast, grid, st, src, apack, table, bias, dst, ps, pq, slab, p); break;
-    case 4: launch_tm<4>(c, fast, grid, st, src, apack, table, bias, dst, ps, pq, slab, p); break;
-    default: launch_tm<5>(c, fast, grid, st, src, apack, table, bias, dst, ps, pq, slab, p); break;
-  }
-  return gca_launch_status();
-}
-
-// leave_slabs: a split-K launch stops before its finishing pass (gca_conv_fwd_slabs: the consumer folds the slabs)
-int run_class(const IgemmCfg& c, int fast, const float* src, const float* apack, const int2* table, const float* bias,
-              float* dst, float* psum, float* psq, float* slab, IgemmParams p, hipStream_t st, bool leave_slabs) {
-  const int tilesN = (int)gca_ceil_div(p.Ntot, c.bn);
+// Completes `p` for a single-phase gather launch of a class: every column tile with the one tile height, each tile's
+// reduction over c.splits workgroups.  -> workgroups of the launch
+inline long long single_phase_setup(const IgemmCfg& c, IgemmParams& p) {
   p.splits = c.splits; p.kt_per_split = c.kt_per_split;
   p.P = stat_parts(c, p.Ntot);
-  if (c.splits > 1 && !slab) return GCA_EINVAL;
-  float* ps = c.splits > 1 ? nullptr : psum;
-  float* pq = c.splits > 1 ? nullptr : psq;
-  if (c.tail_bm > 0) {                       // two-phase: tall tiles over [0, main_cols), short tiles over the rest
-    if ((fast == 1 || fast == 2) && c.tail_bm <= 64) {          // one launch (conv_igemm_2phase_kernel)
-      p.tilesM = (int)gca_ceil_div(p.DK, c.bm); p.tilesN = c.main_cols; p.tileN_off = 0;
-      const int tmB = (int)gca_ceil_div(p.DK, c.tail_bm), tnB = tilesN - c.main_cols;
-      const long long nA = (long long)p.tilesM * p.tilesN, nB = (long long)tmB * tnB;
-      if (nA + nB > 0x7fffffffLL) return GCA_EINVAL;
-      bool done = true;
-#define GCA_2PL(A, B, F, M)                                                                                                  \
-  hipLaunchKernelGGL((conv_igemm_2phase_kernel<A, B, F, M>), dim3((unsigned)(nA + nB)), dim3(256), 0, st, src, apack, table,  \
-                     bias, dst, ps, pq, p, (int)nA, tmB, tnB)
-#define GCA_2P(A, B)                                                                                                          \
-  if (c.bm == 32 * A && c.tail_bm == 32 * B) {                                                                                \
-    if (c.math == 1) { if (fast == 1) GCA_2PL(A, B, 1, 1); else GCA_2PL(A, B, 2, 1); }                                        \
-    else if (c.math == 2) { if (fast == 1) GCA_2PL(A, B, 1, 2); else GCA_2PL(A, B, 2, 2); }                                   \
-    else { if (fast == 1) GCA_2PL(A, B, 1, 0); else GCA_2PL(A, B, 2, 0); }                                                    \
-  } else
-      GCA_2P(2, 1) GCA_2P(3, 1) GCA_2P(3, 2) GCA_2P(4, 1) GCA_2P(4, 2) GCA_2P(5, 1) GCA_2P(5, 2) { done = false; }
-#undef GCA_2P
-#undef GCA_2PL
-      if (done) return gca_launch_status();
-    }
-    p.tilesM = (int)gca_ceil_div(p.DK, c.bm); p.tilesN = c.main_cols; p.tileN_off = 0;
-    int rc = launch_tiles(c.bm, c, fast, dim3((unsigned)((long long)p.tilesM * p.tilesN)), st, src, apack, table, bias, dst, ps, pq,
-                          slab, p);
-    if (rc) return rc;
-    p.tilesM = (int)gca_ceil_div(p.DK, c.tail_bm); p.tilesN = tilesN - c.main_cols; p.tileN_off = c.main_cols;
-    return launch_tiles(c.tail_bm, c, fast, dim3((unsigned)((long long)p.tilesM * p.tilesN)), st, src, apack, table, bias, dst, ps,
-                        pq, slab, p);
-  }
   p.tilesM = (int)gca_ceil_div(p.DK, c.bm);
-  p.tilesN = tilesN;
+  p.tilesN = (int)gca_ceil_div(p.Ntot, c.bn);
   p.tileN_off = 0;
-  const long long nblk = (long long)p.tilesM * p.tilesN * c.splits;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return GCA_EINVAL;
-  int rc = launch_tiles(c.bm, c, fast, dim3((unsigned)nblk), st, src, apack, table, bias, dst, ps, pq, slab, p);
-  if (rc || c.splits == 1 || leave_slabs) return rc;
-  return finish_slabs(c, slab, bias, dst, psum, psq, p, st);
+  return (long long)p.tilesM * p.tilesN * c.splits;
 }
 
-// One class on the LDS-halo kernels.  `tapdelta` = the 64-entry tap-delta table that follows the class's gather rows.
-int run_class_halo(const gca_conv_geom* g, const ClassInfo& c, const IgemmCfg& cf, const float* src, const float* apack,
-                   const int2* table, const float* bias, float* dst, float* psum, float* psq, float* slab, IgemmParams p,
-                   hipStream_t st, bool leave_slabs, const float* in_scale, const float* in_shift) {
+// `nblk` workgroups of tile `t` on conv_igemm_kernel; `o` as tile_operands left it
+int launch_tiles(const TileInst& t, long long nblk, const ConvOperands& o, const IgemmParams& p) {
+  const int rc = with_tile<SINGLE_TILES>(t, [&](auto T) {
+    using K = decltype(T);
+    hipLaunchKernelGGL((conv_igemm_kernel<K::TM, K::BN, K::FAST, K::VEC, K::MATH, K::H>), dim3((unsigned)nblk), dim3(256), 0, o.st,
+                       o.src, o.wpack, o.table, o.bias, o.dst, o.psum, o.psq, o.slab, p);
+    return gca_launch_status();
+  });
+  return rc == TILE_NOT_BUILT ? GCA_EINVAL : rc;
+}
+
+// One class on the gather kernels.  `p` arrives as class_params left it (plus accumulate).
+int run_class(const IgemmCfg& c, int fast, const ConvOperands& ops, IgemmParams p) {
+  if (c.splits > 1 && !ops.slab) return GCA_EINVAL;
+  const ConvOperands o = tile_operands(ops, c.splits);
+  const long long nblk = single_phase_setup(c, p);
+  const TileInst tall = tile_inst(c, fast, c.bm);
+  if (c.tail_bm > 0) {                       // two-phase: tall tiles over [0, main_cols), short tiles over the rest
+    const TileInst tail = tile_inst(c, fast, c.tail_bm);
+    const int tilesN = p.tilesN, tmB = (int)gca_ceil_div(p.DK, c.tail_bm), tnB = tilesN - c.main_cols;
+    p.tilesN = c.main_cols;
+    const long long nA = (long long)p.tilesM * p.tilesN, nB = (long long)tmB * tnB;
+    // one launch (conv_igemm_2phase_kernel) where that kernel is built for the pair, else one launch per phase
+    const int rc2 = with_tile<TWO_PHASE_TILES>(tall, [&](auto A) {
+      return with_tile<TWO_PHASE_TILES>(tail, [&](auto B) {
+        using KA = decltype(A); using KB = decltype(B);
+        if constexpr (two_phase_rows(KA::TM, KB::TM) && KA::FAST == KB::FAST && KA::MATH == KB::MATH) {
+          if (nA + nB > 0x7fffffffLL) return (int)GCA_EINVAL;
+          hipLaunchKernelGGL((conv_igemm_2phase_kernel<KA::TM, KB::TM, KA::FAST, KA::MATH>), dim3((unsigned)(nA + nB)), dim3(256), 0,
+                             o.st, o.src, o.wpack, o.table, o.bias, o.dst, o.psum, o.psq, p, (int)nA, tmB, tnB);
+          return gca_launch_status();
+        } else return TILE_NOT_BUILT;
+      });
+    });
+    if (rc2 != TILE_NOT_BUILT) return rc2;
+    const int rc = launch_tiles(tall, nA, o, p);
+    if (rc) return rc;
+    p.tilesM = tmB; p.tilesN = tnB; p.tileN_off = c.main_cols;
+    return launch_tiles(tail, nB, o, p);
+  }
+  if (nblk <= 0 || nblk > 0x7fffffffLL) return GCA_EINVAL;
+  const int rc = launch_tiles(tall, nblk, o, p);
+  if (rc || c.splits == 1 || ops.leave_slabs) return rc;
+  return finish_slabs(c, ops, p);
+}
+
+// One class on the LDS-halo kernels (the 64-entry tap-delta table follows the class's gather rows).
+int run_class_halo(const gca_conv_geom* g, const ClassInfo& c, const IgemmCfg& cf, const ConvOperands& ops, IgemmParams p) {
   HaloParams hp;
   if (!halo_geometry(c, p, cf.bd, cf.bh, cf.bw, cf.math, hp)) return GCA_EINVAL;
-  hp.in_scale = in_scale; hp.in_shift = in_shift;
-  if (cf.splits > 1 && !slab) return GCA_EINVAL;
+  hp.in_scale = ops.in_scale; hp.in_shift = ops.in_shift;
+  if (cf.splits > 1 && !ops.slab) return GCA_EINVAL;
   hp.g.splits = cf.splits; hp.g.kt_per_split = cf.kt_per_split;
   hp.chunks_per_split = cf.kt_per_split;
   hp.g.tilesM = cdiv(p.DK, cf.bm);
@@ -1273,24 +1287,23 @@ int run_class_halo(const gca_conv_geom* g, const ClassInfo& c, const IgemmCfg& c
   hp.g.tilesN = (int)tn; hp.g.tileN_off = 0;
   hp.g.P = stat_parts(cf, p.Ntot, tn);
   HaloCfg hc{cf.bm, cf.bn, cf.bd, cf.bh, cf.bw, cf.splits, cf.kt_per_split, cf.math};
-  int rc = halo_launch(hc, hp, src, reinterpret_cast<const unsigned char*>(apack), reinterpret_cast<const int*>(table + p.Kpad),
-                       bias, dst, cf.splits > 1 ? nullptr : psum, cf.splits > 1 ? nullptr : psq, slab, st);
-  if (rc || cf.splits == 1 || leave_slabs) return rc;
+  const ConvOperands o = tile_operands(ops, cf.splits);
+  int rc = halo_launch(hc, hp, o.src, reinterpret_cast<const unsigned char*>(o.wpack), reinterpret_cast<const int*>(o.table + p.Kpad),
+                       o.bias, o.dst, o.psum, o.psq, o.slab, o.st);
+  if (rc || cf.splits == 1 || ops.leave_slabs) return rc;
   p.splits = cf.splits; p.P = hp.g.P;
-  return finish_slabs(cf, slab, bias, dst, psum, psq, p, st);
+  return finish_slabs(cf, ops, p);
 }
 
 // A pointwise class on the fp16 GEMM kernel.
-int run_class_pw(const gca_conv_geom* g, int which, const float* src, const float* apack, const float* bias, float* dst, float* psum,
-                 float* psq, const IgemmParams& p, hipStream_t st) {
+int run_class_pw(const gca_conv_geom* g, int which, const ConvOperands& o, const IgemmParams& p) {
   PwParams pw;
   if (!pw_geometry(g, which, p, pw)) return GCA_EINVAL;
-  return pw_launch(pw, src, reinterpret_cast<const unsigned char*>(apack), bias, dst, psum, psq, st);
+  return pw_launch(pw, o.src, reinterpret_cast<const unsigned char*>(o.wpack), o.bias, o.dst, o.psum, o.psq, o.st);
 }
 
 // The forward class on the stem kernel.
-int run_class_stem(const gca_conv_geom* g, const IgemmCfg& cf, const float* src, const float* apack, const float* bias, float* dst,
-                   float* psum, float* psq, const IgemmParams& p, hipStream_t st) {
+int run_class_stem(const gca_conv_geom* g, const IgemmCfg& cf, const ConvOperands& o, const IgemmParams& p) {
   StemParams sp;
   if (!stem_geometry(g, p, cf.math, sp) || sp.bd != cf.bd || sp.bh != cf.bh || sp.bw != cf.bw) return GCA_EINVAL;
   sp.g.splits = 1; sp.g.kt_per_split = sp.nsteps;
@@ -1299,7 +1312,7 @@ int run_class_stem(const gca_conv_geom* g, const IgemmCfg& cf, const float* src,
   if (tn > 0x7fffffffLL) return GCA_EINVAL;
   sp.g.tilesN = (int)tn; sp.g.tileN_off = 0;
   sp.g.P = (int)tn;
-  return stem_launch(cf.math, sp, src, reinterpret_cast<const unsigned char*>(apack), bias, dst, psum, psq, st);
+  return stem_launch(cf.math, sp, o.src, reinterpret_cast<const unsigned char*>(o.wpack), o.bias, o.dst, o.psum, o.psq, o.st);
 }
 
 // Launch plan of one pass (which: 0 forward, 1 dgrad): its problem classes with their kernel parameters and launch
@@ -1309,6 +1322,7 @@ struct ConvLaunch {
   std::vector<ClassInfo> cls;
   std::vector<IgemmParams> p;
   std::vector<IgemmCfg> cf;
+  std::vector<int> fast;        // tap-mask kind of the class (fast_of)
 };
 
 ConvLaunch resolve_launch(const gca_conv_geom* g, int which) {
@@ -1317,31 +1331,37 @@ ConvLaunch resolve_launch(const gca_conv_geom* g, int which) {
   const size_t n = L.cls.size();
   L.p.assign(n, IgemmParams{});
   L.cf.assign(n, IgemmCfg{});
+  L.fast.assign(n, 0);
   for (size_t i = 0; i < n; ++i) {
     if (L.cls[i].ntaps == 0) continue;
     class_params(g, which, L.cls[i], L.p[i]);
     L.cf[i] = cfg_for(g, which, L.cls[i], L.p[i], n);
+    L.fast[i] = fast_of(L.cls[i].ntaps);
   }
   return L;
 }
 
-// Class i of a resolved pass on its kernel family.  `apack` / `table` point at the class's own packed weights / gather rows;
-// leave_slabs and in_scale / in_shift (input transform of gca_conv_fwd_xf) apply to the split-K capable / halo kernels only.
-int run_resolved_class(const gca_conv_geom* g, int which, const ConvLaunch& L, size_t i, const float* src, const float* apack,
-                       const int2* table, const float* bias, float* dst, float* psum, float* psq, float* slab, int accumulate,
-                       hipStream_t st, bool leave_slabs = false, const float* in_scale = nullptr, const float* in_shift = nullptr) {
-  const ClassInfo& c = L.cls[i];
-  const IgemmCfg& cf = L.cf[i];
+// kernel parameters of class i as the plan resolved them, for this call
+inline IgemmParams call_params(const ConvLaunch& L, size_t i, int accumulate) {
   IgemmParams p = L.p[i];
   p.accumulate = accumulate ? 1 : 0;
+  return p;
+}
+
+// Class i of a resolved pass on its kernel family.  `pass`: the operands as the entry point got them (wpack / table are the
+// whole buffers); leave_slabs and in_scale / in_shift apply to the split-K capable / halo kernels only.
+int run_resolved_class(const gca_conv_geom* g, int which, const ConvLaunch& L, size_t i, const ConvOperands& pass, int accumulate) {
+  const ClassInfo& c = L.cls[i];
+  const IgemmCfg& cf = L.cf[i];
+  const ConvOperands o = class_operands(pass, c);
+  const IgemmParams p = call_params(L, i, accumulate);
   switch (cf.kernel) {
-    case ConvKernel::Pointwise: return run_class_pw(g, which, src, apack, bias, dst, psum, psq, p, st);
-    case ConvKernel::Stem: return run_class_stem(g, cf, src, apack, bias, dst, psum, psq, p, st);
-    case ConvKernel::Halo:
-      return run_class_halo(g, c, cf, src, apack, table, bias, dst, psum, psq, slab, p, st, leave_slabs, in_scale, in_shift);
+    case ConvKernel::Pointwise: return run_class_pw(g, which, o, p);
+    case ConvKernel::Stem: return run_class_stem(g, cf, o, p);
+    case ConvKernel::Halo: return run_class_halo(g, c, cf, o, p);
     case ConvKernel::Gather: break;
   }
-  return run_class(cf, fast_of(c.ntaps), src, apack, table, bias, dst, psum, psq, slab, p, st, leave_slabs);
+  return run_class(cf, L.fast[i], o, p);
 }
 
 inline int64_t class_slab_bytes(const IgemmCfg& cf, const IgemmParams& p) {
@@ -1358,39 +1378,17 @@ inline bool dgrad_merge_on() {
   return g_dgrad_merge != 0;
 }
 
-template <int TM, int BN, int FAST, bool VEC>
-void launch_classes_one(int math, bool h, dim3 grid, hipStream_t st, const float* src, const float* apack, const int2* table,
-                        float* dst, float* slab, const ClassBlock& cb) {
-  if (h)
-    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 3, true>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
-  else if (math == 1)
-    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 1>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
-  else if (math == 2)
-    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 2>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
-  else
-    hipLaunchKernelGGL((conv_igemm_classes_kernel<TM, BN, FAST, VEC, 0>), grid, dim3(256), 0, st, src, apack, table, dst, slab, cb);
-}
-
-template <int TM>
-void launch_classes_tm(const IgemmCfg& c, int fast, dim3 grid, hipStream_t st, const float* src, const float* apack,
-                       const int2* table, float* dst, float* slab, const ClassBlock& cb) {
-  if (c.bn == 256) launch_classes_one<TM, 256, 1, true>(c.math, c.h, grid, st, src, apack, table, dst, slab, cb);
-  else if (fast == 1) launch_classes_one<TM, 128, 1, false>(c.math, c.h, grid, st, src, apack, table, dst, slab, cb);
-  else launch_classes_one<TM, 128, 2, false>(c.math, c.h, grid, st, src, apack, table, dst, slab, cb);
-}
-
 // The classes with taps of dgrad plan `L` as ONE tile launch: the by-value class block and what the launch needs.
 struct MergedLaunch {
   ClassBlock cb;
-  IgemmCfg cf;              // the tile instantiation all classes share (of the first class with taps)
-  int fast;
+  TileInst tile;            // the tile instantiation all classes share
   long long wg, parts;      // workgroups of the tile grid, y blocks of the finishing grid (0: no class splits)
   int64_t slab_bytes;       // the slabs of all classes side by side
 };
 
 // -> true when the classes can share a launch: more than one and at most MAX_MERGED_CLASSES classes with taps, all on the
-// gather kernel with the same tile instantiation (rows, columns / float4 gathers, tap-mask kind, arithmetic, storage) and
-// single-phase.  Tap count, column count, tile counts and split factor are per-class run-time data.
+// gather kernel with the same tile instantiation, one the merged kernel is built for, and single-phase.  Tap count, column
+// count, tile counts and split factor are per-class run-time data.
 bool plan_merged(const ConvLaunch& L, int accumulate, MergedLaunch& m) {
   m = MergedLaunch{};
   ClassBlock& cb = m.cb;
@@ -1406,18 +1404,12 @@ bool plan_merged(const ConvLaunch& L, int accumulate, MergedLaunch& m) {
   for (const size_t i : order) {
     const ClassInfo& c = L.cls[i];
     const IgemmCfg& cf = L.cf[i];
-    const int fast = fast_of(c.ntaps);
-    if (n == MAX_MERGED_CLASSES || cf.kernel != ConvKernel::Gather || cf.tail_bm > 0 || fast == 0) return false;
-    if (n == 0) { m.cf = cf; m.fast = fast; }
-    else if (cf.bm != m.cf.bm || cf.bn != m.cf.bn || fast != m.fast || cf.math != m.cf.math || cf.h != m.cf.h) return false;
-    IgemmParams p = L.p[i];                      // (as run_class sets a single-phase launch up)
-    p.accumulate = accumulate ? 1 : 0;
-    p.splits = cf.splits; p.kt_per_split = cf.kt_per_split;
-    p.P = stat_parts(cf, p.Ntot);
-    p.tilesM = (int)gca_ceil_div(p.DK, cf.bm);
-    p.tilesN = (int)gca_ceil_div(p.Ntot, cf.bn);
-    p.tileN_off = 0;
-    const long long nblk = (long long)p.tilesM * p.tilesN * cf.splits;
+    if (n == MAX_MERGED_CLASSES || cf.kernel != ConvKernel::Gather || cf.tail_bm > 0) return false;
+    const TileInst t = tile_inst(cf, L.fast[i], cf.bm);
+    if (n == 0 ? !tile_built<MERGED_TILES>(t) : !(t == m.tile)) return false;
+    m.tile = t;
+    IgemmParams p = call_params(L, i, accumulate);
+    const long long nblk = single_phase_setup(cf, p);
     if (nblk <= 0 || (n > 0 && p.DK != cb.p[0].DK)) return false;
     cb.p[n] = p;
     cb.pack_off[n] = c.pack_off;
@@ -1439,41 +1431,41 @@ bool plan_merged(const ConvLaunch& L, int accumulate, MergedLaunch& m) {
   return true;
 }
 
-// One tile launch plus (where classes split the reduction) one finishing launch.
-int run_classes_merged(const MergedLaunch& m, const float* dy, const float* wpack, const int2* tab, float* dx, float* ws,
-                       hipStream_t st) {
+// One tile launch plus (where classes split the reduction) one finishing launch.  `o`: the pass's operands (the kernels
+// apply the class block's per-class offsets themselves).
+int run_classes_merged(const MergedLaunch& m, const ConvOperands& o) {
   const ClassBlock& cb = m.cb;
-  const dim3 grid((unsigned)m.wg);
-  switch (m.cf.bm / 32) {
-    case 1: launch_classes_tm<1>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
-    case 2: launch_classes_tm<2>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
-    case 3: launch_classes_tm<3>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
-    case 4: launch_classes_tm<4>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
-    default: launch_classes_tm<5>(m.cf, m.fast, grid, st, dy, wpack, tab, dx, ws, cb); break;
-  }
-  const int rc = gca_launch_status();
+  const int rc = with_tile<MERGED_TILES>(m.tile, [&](auto T) {
+    using K = decltype(T);
+    hipLaunchKernelGGL((conv_igemm_classes_kernel<K::TM, K::BN, K::FAST, K::VEC, K::MATH, K::H>), dim3((unsigned)m.wg), dim3(256), 0,
+                       o.st, o.src, o.wpack, o.table, o.dst, o.slab, cb);
+    return gca_launch_status();
+  });
+  if (rc == TILE_NOT_BUILT) return GCA_EINVAL;
   if (rc || m.parts == 0) return rc;
   const dim3 fgrid((unsigned)cb.p[0].DK, (unsigned)m.parts);
-  if (m.cf.h)
-    hipLaunchKernelGGL(conv_splitk_finish_classes_kernel<_Float16>, fgrid, dim3(256), 0, st, ws, reinterpret_cast<_Float16*>(dx), cb);
+  if (m.tile.math == 3)
+    hipLaunchKernelGGL(conv_splitk_finish_classes_kernel<_Float16>, fgrid, dim3(256), 0, o.st, o.slab, reinterpret_cast<_Float16*>(o.dst), cb);
   else
-    hipLaunchKernelGGL(conv_splitk_finish_classes_kernel<float>, fgrid, dim3(256), 0, st, ws, dx, cb);
+    hipLaunchKernelGGL(conv_splitk_finish_classes_kernel<float>, fgrid, dim3(256), 0, o.st, o.slab, o.dst, cb);
   return gca_launch_status();
 }
 
-int64_t ws_bytes_for(const gca_conv_geom* g, int which) {
-  const ConvLaunch L = resolve_launch(g, which);
-  int64_t need = 0;
-  for (size_t i = 0; i < L.cls.size(); ++i)
-    if (L.cf[i].splits > 1) need = std::max<int64_t>(need, (int64_t)L.cf[i].splits * L.p[i].DK * L.p[i].Ntot * (int64_t)sizeof(float));
-  return need;
+// -> true when resolved dgrad `L` runs as one merged launch (planned into `m`) with a work space of ws_bytes: the slabs of
+// all split classes must fit side by side; a merged launch with no split class needs no work space at all
+bool dgrad_runs_merged(const ConvLaunch& L, int accumulate, bool have_ws, int64_t ws_bytes, MergedLaunch& m) {
+  return L.cls.size() > 1 && dgrad_merge_on() && plan_merged(L, accumulate, m) &&
+         (m.slab_bytes == 0 || (have_ws && ws_bytes >= m.slab_bytes));
 }
 
-// the slabs of all classes side by side (what the merged dgrad launch needs); never less than ws_bytes_for
-int64_t ws_bytes_merged_for(const gca_conv_geom* g, int which) {
+// work space of a pass: the slabs of its largest class, or (side_by_side: what the merged dgrad launch needs) of all classes
+int64_t ws_bytes_for(const gca_conv_geom* g, int which, bool side_by_side = false) {
   const ConvLaunch L = resolve_launch(g, which);
   int64_t need = 0;
-  for (size_t i = 0; i < L.cls.size(); ++i) need += class_slab_bytes(L.cf[i], L.p[i]);
+  for (size_t i = 0; i < L.cls.size(); ++i) {
+    const int64_t b = class_slab_bytes(L.cf[i], L.p[i]);
+    need = side_by_side ? need + b : std::max(need, b);
+  }
   return need;
 }
 
@@ -1666,7 +1658,7 @@ int gca_conv_kernel_cfg(const gca_conv_geom* g, int which, int32_t* out4) {
     const IgemmCfg& cf = L.cf[i];
     if (c.ntaps == 0) continue;
     out4[0] = cf.bm; out4[1] = cf.bn; out4[2] = cf.splits;
-    out4[3] = (int)L.cls.size() | (fast_of(c.ntaps) << 8) | (c.vec << 10) | (cf.math << 12) | ((cf.kernel == ConvKernel::Halo) << 14) |
+    out4[3] = (int)L.cls.size() | (L.fast[i] << 8) | (c.vec << 10) | (cf.math << 12) | ((cf.kernel == ConvKernel::Halo) << 14) |
               (cf.h << 15) | ((cf.kernel == ConvKernel::Stem) << 16) | ((cf.kernel == ConvKernel::Pointwise) << 17);
     return GCA_OK;
   }
@@ -1691,8 +1683,9 @@ int gca_conv_fwd(const gca_conv_geom* g, const void* x_, const float* wpack, con
   float* y = reinterpret_cast<float*>(y_);
   if (!geom_ok(g) || !x || !wpack || !table || !y) return GCA_EINVAL;
   if ((stat_sum == nullptr) != (stat_sq == nullptr)) return GCA_EINVAL;
-  return run_resolved_class(g, 0, resolve_launch(g, 0), 0, x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum,
-                            stat_sq, reinterpret_cast<float*>(ws), 0, (hipStream_t)stream);
+  const ConvOperands o{x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum, stat_sq, reinterpret_cast<float*>(ws),
+                       (hipStream_t)stream};
+  return run_resolved_class(g, 0, resolve_launch(g, 0), 0, o, 0);
 }
 
 int gca_conv_fwd_slabs(const gca_conv_geom* g, const void* x, const float* wpack, const int32_t* table, void* ws,
@@ -1704,8 +1697,10 @@ int gca_conv_fwd_slabs(const gca_conv_geom* g, const void* x, const float* wpack
   // must use gca_conv_fwd)
   if ((cf.kernel != ConvKernel::Gather && cf.kernel != ConvKernel::Halo) || cf.splits < 2) return GCA_EINVAL;
   float* slab = reinterpret_cast<float*>(ws);           // (the destination is never written in this mode)
-  const int rc = run_resolved_class(g, 0, L, 0, reinterpret_cast<const float*>(x), wpack, reinterpret_cast<const int2*>(table),
-                                    nullptr, slab, nullptr, nullptr, slab, 0, (hipStream_t)stream, true);
+  ConvOperands o{reinterpret_cast<const float*>(x), wpack, reinterpret_cast<const int2*>(table), nullptr, slab, nullptr, nullptr,
+                 slab, (hipStream_t)stream};
+  o.leave_slabs = true;
+  const int rc = run_resolved_class(g, 0, L, 0, o, 0);
   if (rc) return rc;
   *out_splits = cf.splits;
   return GCA_OK;
@@ -1726,17 +1721,19 @@ int gca_conv_fwd_xf(const gca_conv_geom* g, const void* x_, const float* in_scal
   if ((stat_sum == nullptr) != (stat_sq == nullptr)) return GCA_EINVAL;
   const ConvLaunch L = resolve_launch(g, 0);
   if (L.cf[0].kernel != ConvKernel::Halo) return GCA_EINVAL;    // only the LDS-halo kernels stage their input through registers
-  return run_resolved_class(g, 0, L, 0, x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum, stat_sq,
-                            reinterpret_cast<float*>(ws), 0, (hipStream_t)stream, false, in_scale, in_shift);
+  ConvOperands o{x, wpack, reinterpret_cast<const int2*>(table), bias, y, stat_sum, stat_sq, reinterpret_cast<float*>(ws),
+                 (hipStream_t)stream};
+  o.in_scale = in_scale; o.in_shift = in_shift;
+  return run_resolved_class(g, 0, L, 0, o, 0);
 }
 
-int64_t gca_conv_dgrad_ws_bytes_merged(const gca_conv_geom* g) { return geom_ok(g) ? ws_bytes_merged_for(g, 1) : GCA_EINVAL; }
+int64_t gca_conv_dgrad_ws_bytes_merged(const gca_conv_geom* g) { return geom_ok(g) ? ws_bytes_for(g, 1, true) : GCA_EINVAL; }
 int64_t gca_conv_class_block_bytes(void) { return (int64_t)sizeof(ClassBlock); }
 int gca_conv_dgrad_merged(const gca_conv_geom* g, int64_t ws_bytes) {
   if (!geom_ok(g)) return GCA_EINVAL;
   const ConvLaunch L = resolve_launch(g, 1);
   MergedLaunch m;
-  return L.cls.size() > 1 && dgrad_merge_on() && plan_merged(L, 0, m) && ws_bytes >= m.slab_bytes;
+  return dgrad_runs_merged(L, 0, true, ws_bytes, m);
 }
 
 int gca_set_dgrad_merge(int on) {
@@ -1763,15 +1760,13 @@ int gca_conv_dgrad_ws(const gca_conv_geom* g, const void* dy_, const float* wpac
     hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<unsigned*>(dx), n32,
                        g->act_f16 ? (int)(n & 1) : 0);
   }
-  const int2* tab = reinterpret_cast<const int2*>(table);
+  const ConvOperands o{dy, wpack, reinterpret_cast<const int2*>(table), nullptr, dx, nullptr, nullptr, reinterpret_cast<float*>(ws),
+                       st};
   MergedLaunch m;          // strided: every class with taps in one launch where they allow it and `ws` holds all their slabs
-  if (L.cls.size() > 1 && dgrad_merge_on() && plan_merged(L, accumulate, m) && (m.slab_bytes == 0 || (ws && ws_bytes >= m.slab_bytes)))
-    return run_classes_merged(m, dy, wpack, tab, dx, reinterpret_cast<float*>(ws), st);
+  if (dgrad_runs_merged(L, accumulate, ws != nullptr, ws_bytes, m)) return run_classes_merged(m, o);
   for (size_t i = 0; i < L.cls.size(); ++i) {
-    const ClassInfo& c = L.cls[i];
-    if (c.ntaps == 0) continue;
-    const int rc = run_resolved_class(g, 1, L, i, dy, wpack + c.pack_off, tab + c.table_off, nullptr, dx, nullptr, nullptr,
-                                      reinterpret_cast<float*>(ws), accumulate, st);
+    if (L.cls[i].ntaps == 0) continue;
+    const int rc = run_resolved_class(g, 1, L, i, o, accumulate);
     if (rc) return rc;
   }
   return GCA_OK;

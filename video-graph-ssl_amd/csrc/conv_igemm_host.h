@@ -62,6 +62,27 @@ struct ClassInfo {
   bool vec;
 };
 
+// ---- operands of the forward / dgrad launch path -------------------------------------------------
+// What an entry point hands down to the launchers.  wpack / table are the pass's buffers at the entry point and the class's
+// own packed weights / gather rows once class_operands has applied the class's offsets.
+struct ConvOperands {
+  const float* src; const float* wpack; const int2* table; const float* bias;
+  float* dst; float* psum; float* psq; float* slab;
+  hipStream_t st;
+  bool leave_slabs = false;                  // a split-K launch stops before its finishing pass (gca_conv_fwd_slabs: the consumer folds the slabs)
+  const float* in_scale = nullptr; const float* in_shift = nullptr;     // input transform of gca_conv_fwd_xf (LDS-halo kernels only)
+};
+inline ConvOperands class_operands(ConvOperands o, const ClassInfo& c) {
+  o.wpack += c.pack_off; o.table += c.table_off;
+  return o;
+}
+// A launch that splits the reduction leaves fp32 slabs: its tile kernel emits no statistics (null stat pointers), the
+// finishing pass gets the real ones.
+inline ConvOperands tile_operands(ConvOperands o, int splits) {
+  if (splits > 1) o.psum = o.psq = nullptr;
+  return o;
+}
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int fast_of(int ntaps) { return ntaps <= 31 ? 1 : (ntaps <= FAST_MAX_TAPS ? 2 : 0); }
 inline int pack_rows(int M) { return (int)gca_round_up(M, 32) + 128; }   // every tile height up to 160 stays in bounds
