@@ -537,6 +537,35 @@ int gca_knn_vote(const int32_t* idx, const float* dist, int64_t nq, int32_t k, i
                  int32_t weighting, float inv_T, float* scores, int32_t* pred, int32_t* rank, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * NT-Xent: SimCLR's in-batch contrastive loss and its gradient (csrc/ntxent.hip).  The reference trains with a MoCo queue
+ * or SimSiam only; this is the objective its LARS-era relatives use (every other clip of the batch is a negative, no queue,
+ * no momentum encoder), on the reference's own encoder + 'mlp' head + Normalize (lib/modeling/graph_wrappers.py:9-27).
+ *   z (N, D) fp32, N = 2b: rows 0..b-1 are view 1, rows b..2b-1 are view 2;  pos(i) = (i + b) mod N
+ *   s[i,j]  = (sum_d z[i,d] * z[j,d]) * inv_T
+ *   lse[i]  = m_i + log sum_{j != i} exp(s[i,j] - m_i),  m_i = max_{j != i} s[i,j]      (rows need not be unit-norm)
+ *   sp[i]   = s[i, pos(i)]
+ *   loss    = (1/N) sum_i (lse[i] - sp[i])
+ *   rank[i] = #{ j : j != i, j != pos(i), s[i,j] >= sp[i] }          (top-k hit iff rank < k, as rank_ge of the InfoNCE entry)
+ *   P[i,j]  = exp(s[i,j] - lse[i]) for j != i, 0 on the diagonal
+ *   dz[i,:] = g * inv_T / N * ( sum_j (P[i,j] + P[j,i]) z[j,:] - 2 z[pos(i),:] ),   g = gscale_host * (gscale_dev ? *gscale_dev : 1)
+ * Products on v_mfma_f32_32x32x2_f32 (exact fp32, fp32 accumulation); sp[i] is computed by the same fma chain as the
+ * streamed s[i,pos(i)], so ties with the positive compare equal.  No N x N tensor, no atomics: outputs are bitwise the same
+ * from call to call.  No host sync, allocation or read: both entries can be captured in a hipGraph.  Launches: forward 2
+ * (tiles, then the fold of the column splits + loss), backward 2 (tiles, then the fold of the row splits + scale).
+ * pos_logit and rank_ge may be NULL.  `ws`: gca_ntxent_ws_bytes(N, D) bytes (always > 0 for valid sizes), shared by both.
+ * gca_ntxent_path reports the dispatch for these sizes (`aligned`: z, dz and ws 16-byte aligned): returns 1 for the fast path
+ * (D <= 128, D % 4 == 0, aligned; 4 waves per workgroup), 0 for the generic one (1 wave), and writes the waves per workgroup
+ * and the number of tile splits when the pointers are non-NULL.  tests/ntxent_ref.py restates arithmetic and dispatch.
+ * GCA_EINVAL (nothing launched, nothing written; -1 from gca_ntxent_ws_bytes) for N odd, N < 2, N > 65536, D < 1,
+ * N * D >= 2^31, inv_T not finite or <= 0, a NULL z / row_lse / loss / dz / ws. */
+int64_t gca_ntxent_ws_bytes(int64_t N, int64_t D);
+int gca_ntxent_path(int64_t N, int64_t D, int aligned, int32_t* waves, int32_t* splits);
+int gca_ntxent_fwd(const float* z, int64_t N, int64_t D, float inv_T, float* row_lse, float* pos_logit, int32_t* rank_ge,
+                   float* loss, void* ws, void* stream);
+int gca_ntxent_bwd(const float* z, const float* row_lse, int64_t N, int64_t D, float inv_T, const float* gscale_dev,
+                   float gscale_host, float* dz, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

@@ -895,6 +895,49 @@ def knn_vote(idx, dist, g_label, num_class, kvote=None, q_label=None, self_base=
     return pred, rank, scores
 
 
+# ----------------------------------------------------------------------------- NT-Xent (SimCLR)
+def _ntxent_args(z, inv_T, what):
+    """Host-side refusals of gca_ntxent_fwd / _bwd (before any device is touched) -> (N, D, inv_T)."""
+    if z.dim() != 2 or z.dtype is not F32:
+        raise ValueError('%s: z is a (N, D) fp32 matrix (got %s %s)' % (what, tuple(z.shape), z.dtype))
+    N, D = z.shape
+    if N < 2 or N % 2 or N > 65536 or D < 1 or N * D >= 2 ** 31:
+        raise ValueError('%s: N must be even, 2 <= N <= 65536, D >= 1, N * D < 2^31 (got N=%d, D=%d)' % (what, N, D))
+    inv_T = float(inv_T)
+    if not 0.0 < inv_T < 3.0e38:
+        raise ValueError('%s: 1 / T must be positive and finite in fp32 (got %r)' % (what, inv_T))
+    return N, D, inv_T
+
+
+def ntxent_fwd(z, inv_T, want_rank=False):
+    """NT-Xent forward (gca_ntxent_fwd; tests/ntxent_ref.py states the arithmetic): z (N, D) fp32 with rows 0..N/2-1 view 1 and
+    N/2..N-1 view 2 -> (loss (1,), lse (N,), rank (N,) int32 or None), all on the device.  rank[i] counts the negatives of
+    row i that score at least its positive (top-k hit iff rank < k).  ValueError for arguments the kernel entry refuses."""
+    N, D, inv_T = _ntxent_args(z, inv_T, 'ntxent_fwd')
+    z = z.contiguous()
+    pz = ptr(z)                                                         # (RuntimeError for host tensors)
+    dev = z.device
+    loss = torch.empty(1, dtype=F32, device=dev)
+    lse = torch.empty(N, dtype=F32, device=dev)
+    rank = torch.empty(N, dtype=torch.int32, device=dev) if want_rank else None
+    ws = WS.get(H.lib.gca_ntxent_ws_bytes(N, D), dev)
+    H.call('gca_ntxent_fwd', pz, N, D, inv_T, ptr(lse), None, ptr(rank), ptr(loss), ptr(ws), stream())
+    return loss, lse, rank
+
+
+def ntxent_bwd(z, lse, inv_T, gscale_dev=None, gscale_host=1.0):
+    """d loss / d z of ntxent_fwd from its row log-sum-exps, times gscale_host * (*gscale_dev if given) -> dz (N, D)."""
+    N, D, inv_T = _ntxent_args(z, inv_T, 'ntxent_bwd')
+    if lse.dtype is not F32 or tuple(lse.shape) != (N,):
+        raise ValueError('ntxent_bwd: lse is the (N,) fp32 vector of ntxent_fwd (got %s %s)' % (tuple(lse.shape), lse.dtype))
+    z, lse = z.contiguous(), lse.contiguous()
+    pz, pl = ptr(z), ptr(lse)
+    dz = torch.empty((N, D), dtype=F32, device=z.device)
+    ws = WS.get(H.lib.gca_ntxent_ws_bytes(N, D), z.device)
+    H.call('gca_ntxent_bwd', pz, pl, N, D, inv_T, ptr(gscale_dev), float(gscale_host), ptr(dz), ptr(ws), stream())
+    return dz
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

@@ -1,4 +1,4 @@
-"""Pre-training step drivers (MoCo and SimSiam) on the HIP engine.
+"""Pre-training step drivers (MoCo, SimSiam and SimCLR) on the HIP engine.
 
 Restates the iteration of tools/train_video_contrast_dis.py:395-454 (_train_moco) and :479-523
 (_train_simsiam) without its host syncs (3x .item() per iteration, :429-431) and defects
@@ -460,19 +460,23 @@ class MoCoTrainer(_TrainerBase):
         return int(sd.get('epoch', 0))
 
 
-class SimSiamTrainer(_TrainerBase):
+class _TwoViewTrainer(_TrainerBase):
+    """One encoder, both views of a (b, 6, T, H, W) batch through it with gradients, a loss formed inside the model
+    (``model.fwd`` returns the loss Var): the step that SimSiamTrainer and SimCLRTrainer share.  A subclass checks its
+    configuration (_check_cfg / _check_model) and says what a step reports (_outputs)."""
+
     def __init__(self, cfg, device, ctx=None, use_graph=True, seed=None):
         _check_unsupported(cfg)
         self.cfg, self.device = cfg, torch.device(device)
         self.clip = clip_value_of(cfg)
         self.ctx = ctx or par.DistCtx()
+        self._check_cfg(cfg)
         ls = _loss_scale()
         self.scale_state = None if ls is None else ops.loss_scale_state(ls, torch.device(device))
         if seed is not None:
             torch.manual_seed(seed)
         self.model, ema = create_visual_model(cfg)
-        if ema is not None:
-            raise ValueError('SimSiamTrainer needs CONTRAST.MEM_TYPE == simsiam')
+        self._check_model(ema)
         self.model.to(self.device)
         self.arena = arena_of(self.model)
         par.broadcast_(self.arena.flat, self.ctx)
@@ -484,6 +488,15 @@ class SimSiamTrainer(_TrainerBase):
         self._buckets, self._planned, self._tape = None, False, None     # N > 1: gradient buckets (see MoCoTrainer)
         self._reducer = par.BucketReducer(self.arena.grad, self.ctx)
 
+    def _check_cfg(self, cfg):
+        pass
+
+    def _check_model(self, ema):
+        pass
+
+    def _outputs(self, lv):
+        return dict(loss=lv.t)
+
     def _fwd_bwd(self, upto=0):
         """Forward, loss and the backward pass down to tape index `upto` (0 = all of it; N > 1 runs the rest in stages)."""
         self.optimizer.zero_grad()
@@ -491,8 +504,8 @@ class SimSiamTrainer(_TrainerBase):
             self._packer.run()
         tape = Tape(True)
         lv = self.model.fwd(tape, Var(self._static))
-        self.out = dict(loss=lv.t)
-        ops.LOSS_SCALE_STATE[0] = self.scale_state            # fp16 storage: SimSiam.fwd's loss-gradient seed is scaled by S
+        self.out = self._outputs(lv)
+        ops.LOSS_SCALE_STATE[0] = self.scale_state            # fp16 storage: the model's loss-gradient seed is scaled by S
         try:
             self._backward(tape, upto)
         finally:
@@ -586,8 +599,9 @@ class SimSiamTrainer(_TrainerBase):
         return self.out
 
     def state_dict(self, epoch=0):
-        """Checkpoint dict with the reference's keys (tools/...dis.py:274-286; SimSiam has no memory, so `contrast` is None
-        as the reference writes it).  ActionTrainer.load_pretrained and lib.evaluation.load_encoder read its `state_dict`."""
+        """Checkpoint dict with the reference's keys (tools/...dis.py:274-286; neither SimSiam nor SimCLR has a memory, so
+        `contrast` is None as the reference writes it).  ActionTrainer.load_pretrained and lib.evaluation.load_encoder read its
+        `state_dict`."""
         return {'epoch': epoch, 'state_dict': self.model.state_dict(), 'optimizer': self.optimizer.state_dict(), 'contrast': None,
                 **({} if self.scale_state is None else {'loss_scale_state': self.scale_state.detach().cpu().clone()})}
 
@@ -599,6 +613,31 @@ class SimSiamTrainer(_TrainerBase):
         if self.scale_state is not None and sd.get('loss_scale_state') is not None:
             self.scale_state.copy_(sd['loss_scale_state'])
         return int(sd.get('epoch', 0))
+
+
+class SimSiamTrainer(_TwoViewTrainer):
+    """tools/train_video_contrast_dis.py:479-523 (_train_simsiam): CONTRAST.MEM_TYPE 'simsiam'."""
+
+    def _check_model(self, ema):
+        if ema is not None:
+            raise ValueError('SimSiamTrainer needs CONTRAST.MEM_TYPE == simsiam')
+
+
+class SimCLRTrainer(_TwoViewTrainer):
+    """In-batch contrastive pre-training (NT-Xent; CONTRAST.MEM_TYPE 'simclr', temperature CONTRAST.NCE_T): SimSiamTrainer's
+    step with lib.modeling.graph_wrappers.SimCLR as the model.  `out` carries `loss` and `rank` (per row of the 2b views, the
+    negatives that score at least the positive: a top-k hit iff rank < k).  One GPU only: global negatives need an all-gather
+    of the features and an exchange of their gradients."""
+
+    def _check_cfg(self, cfg):
+        if cfg.CONTRAST.MEM_TYPE != 'simclr':
+            raise ValueError('SimCLRTrainer needs CONTRAST.MEM_TYPE == simclr (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if self.ctx.active:
+            raise NotImplementedError('SimCLRTrainer runs on one GPU: NT-Xent over the global batch needs a feature all-gather '
+                                      'and a gradient exchange between the ranks')
+
+    def _outputs(self, lv):
+        return dict(loss=lv.t, rank=self.model.model.rank)
 
 
 class ActionTrainer(_TrainerBase):

@@ -1,7 +1,9 @@
 """Factories (reference: lib/memory/build.py).  Only what the pre-training configs select is on the
-HIP path: MEM_TYPE 'moco' (visual) / 'simsiam', CRITERION 'crossentropy'."""
+HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no memory, the loss module itself),
+CRITERION 'crossentropy'."""
 from .criterion import NCESoftmaxLoss
 from .mem_moco import RGBMoCo
+from .ntxent import NTXent
 
 
 def create_contrast(cfg, n_data):
@@ -11,6 +13,8 @@ def create_contrast(cfg, n_data):
         return RGBMoCo(cfg.CROSS.FEAT_DIM, cfg.CONTRAST.NCE_K, cfg.CONTRAST.NCE_T)
     if cfg.CONTRAST.MEM_TYPE == 'simsiam':
         return None
+    if cfg.CONTRAST.MEM_TYPE == 'simclr':
+        return NTXent(cfg.CONTRAST.NCE_T)
     raise NotImplementedError('mem not suported: {}'.format(cfg.CONTRAST.MEM_TYPE))
 
 

@@ -1,7 +1,8 @@
-"""ContrastWrapper / SimSiam / GraphWrapper (reference: lib/modeling/graph_wrappers.py) on the engine.
+"""ContrastWrapper / SimSiam / GraphWrapper (reference: lib/modeling/graph_wrappers.py) on the engine, and SimCLR (the
+reference's ContrastWrapper trained with the in-batch NT-Xent loss; not in the reference).
 
 ``GraphWrapper.forward(x)`` keeps the reference behaviour (MoCo: (b,3,T,H,W) -> (b,FEAT_DIM) unit
-rows; SimSiam: (b,6,T,H,W) -> scalar loss) and is differentiable through torch.autograd as ONE
+rows; SimSiam and SimCLR: (b,6,T,H,W) -> scalar loss) and is differentiable through torch.autograd as ONE
 node (engine/autograd_bridge.py); the trainer's fused step calls ``fwd`` directly."""
 import torch
 import torch.nn as nn
@@ -80,11 +81,56 @@ class SimSiam(nn.Module):
         return run_module(self, x).reshape(())
 
 
+class SimCLR(ContrastWrapper):
+    """ContrastWrapper (encoder + projection head + Normalize) trained with NT-Xent on the two views of a (b,6,T,H,W) batch.
+    No parameters or buffers of its own: the state dict is ContrastWrapper's (``encoder.*``, ``proj_head.*``), so every
+    loader of MoCo checkpoints reads it.  The views go through encoder + head in TWO passes, so BatchNorm statistics are per
+    view (as in this package's SimSiam and in MoCo v3), not over the concatenated 2b clips as in SimCLR's own code."""
+
+    def __init__(self, encoder, hid_dim=128, head_type='mlp', T=0.07):
+        super().__init__(encoder, hid_dim, head_type)
+        T = float(T)
+        if not T > 0:
+            raise ValueError('SimCLR: the temperature must be positive (got %r)' % T)
+        self.T, self.rank = T, None          # rank: per row, the negatives that score at least the positive (last forward)
+
+    def fwd(self, tape, xv):
+        """loss = NT-Xent(z1, z2) over the N = 2b rows, both views through the encoder WITH grad."""
+        x = xv.t
+        x1, x2 = torch.chunk(x, 2, dim=1)          # views, read in place through the batch stride
+        z1 = ContrastWrapper.fwd(self, tape, Var(x1))
+        z2 = ContrastWrapper.fwd(self, tape, Var(x2))
+        b, dim = z1.t.shape
+        z = torch.empty((2 * b, dim), dtype=torch.float32, device=x.device)
+        z[:b].copy_(z1.t)
+        z[b:].copy_(z2.t)
+        inv_T = 1.0 / self.T
+        loss, lse, self.rank = ops.ntxent_fwd(z, inv_T, want_rank=True)
+        lv = Var(loss, tape.recording)
+
+        def back():
+            # d loss / d z in one launch pair; the upstream scalar and the fp16-storage loss scale fold into its scale
+            g = lv.grad
+            gs = 1.0
+            if g is not None and g.numel() == 1 and not torch.cuda.is_current_stream_capturing():
+                gs = float(g.item())
+            dz = ops.ntxent_bwd(z, lse, inv_T, gscale_dev=ops.LOSS_SCALE_STATE[0], gscale_host=gs)
+            z1.add_grad(dz[:b])                      # the two halves of one buffer: no copy
+            z2.add_grad(dz[b:])
+        tape.record(back)
+        return lv
+
+    def forward(self, x):
+        return run_module(self, x).reshape(())
+
+
 class GraphWrapper(nn.Module):
-    def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam'):
+    def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07):
         super().__init__()
         if mem_type == 'simsiam':
             self.model = SimSiam(encoder=encoder, hid_dim=hid_dim)
+        elif mem_type == 'simclr':
+            self.model = SimCLR(encoder=encoder, hid_dim=hid_dim, head_type=head_type, T=nce_t)
         else:
             self.model = ContrastWrapper(encoder=encoder, hid_dim=hid_dim, head_type=head_type)
 
