@@ -566,6 +566,37 @@ int gca_ntxent_bwd(const float* z, const float* row_lse, int64_t N, int64_t D, f
                    float gscale_host, float* dz, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Barlow Twins: the cross-correlation (redundancy-reduction) loss of two views and its gradient (csrc/barlow.hip).  Not in
+ * the reference; it needs no negatives, queue, momentum encoder or predictor.  z1, z2 (N, D) fp32 contiguous: the projector
+ * outputs of view 1 / view 2 of the same N clips.  Per view v and column d, in two passes:
+ *   mean_v[d] = (sum_n z_v[n,d]) / N      var_v[d] = (sum_n (z_v[n,d] - mean_v[d])^2) / N      rstd_v[d] = 1 / sqrt(var_v[d] + eps)
+ *   a = (z1 - mean_1) * rstd_1            b = (z2 - mean_2) * rstd_2          (BatchNorm1d(affine=False); never stored)
+ *   C[i,j]  = (sum_n a[n,i] * b[n,j]) / N
+ *   on = sum_i (C[i,i] - 1)^2             off = sum_{i != j} C[i,j]^2         loss = on + lambda * off
+ *   G[i,j]  = 2 (C[i,i] - 1) if i == j else 2 lambda C[i,j]                   (formed from cmat on load; never stored)
+ *   r1[i]   = sum_j G[i,j] C[i,j]         r2[j] = sum_i G[i,j] C[i,j]
+ *   dz1[n,i] = g * rstd_1[i] / N * (sum_j G[i,j] b[n,j] - a[n,i] r1[i])
+ *   dz2[n,j] = g * rstd_2[j] / N * (sum_i G[i,j] a[n,i] - b[n,j] r2[j]),      g = gscale_host * (gscale_dev ? *gscale_dev : 1)
+ * the full gradient through the standardisation (its mean term vanishes: a and b have zero column means).
+ * Saved state, caller-owned, written by the forward and read by the backward: stats (4, D) = mean_1, rstd_1, mean_2, rstd_2;
+ * cmat (D, D) = C, 4 D^2 bytes; rsum (2, D) = r1, r2.  loss[3] = loss, on, off.  `ws`: gca_barlow_ws_bytes(N, D) bytes
+ * (always > 0 for valid sizes) of scratch; nothing survives in it between the two entries.
+ * Products on v_mfma_f32_32x32x2_f32 (exact fp32, fp32 accumulation).  No atomics: outputs are bitwise the same from call to
+ * call.  No host sync, allocation or read: both entries can be captured in a hipGraph.  Launches: forward 3 (column
+ * statistics; C tiles with per-tile partials of on / off / r1 / r2; their fold), backward 1 (both views).  One dispatch path
+ * (guarded 4-byte accesses, no alignment assumed).  tests/barlow_ref.py restates the arithmetic.
+ * eps == 0 with a constant column gives var = 0, rstd = inf and inf / NaN outputs by the formula: the caller's business, not
+ * a refusal.
+ * GCA_EINVAL (nothing launched, nothing written; -1 from gca_barlow_ws_bytes) for N < 2, N > 65536, D < 1, D > 8192,
+ * N * D >= 2^31, lambda or eps negative or not finite, gscale_host not finite, any NULL pointer other than gscale_dev. */
+int64_t gca_barlow_ws_bytes(int64_t N, int64_t D);
+int gca_barlow_fwd(const float* z1, const float* z2, int64_t N, int64_t D, float lambda, float eps, float* stats, float* cmat,
+                   float* rsum, float* loss, void* ws, void* stream);
+int gca_barlow_bwd(const float* z1, const float* z2, const float* stats, const float* cmat, const float* rsum, int64_t N,
+                   int64_t D, float lambda, const float* gscale_dev, float gscale_host, float* dz1, float* dz2, void* ws,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

@@ -938,6 +938,61 @@ def ntxent_bwd(z, lse, inv_T, gscale_dev=None, gscale_host=1.0):
     return dz
 
 
+# ----------------------------------------------------------------------------- Barlow Twins
+def _barlow_args(z1, z2, lambd, eps, what):
+    """Host-side refusals of gca_barlow_fwd / _bwd (before any device is touched) -> (N, D, lambda, eps)."""
+    for z in (z1, z2):
+        if z.dim() != 2 or z.dtype is not F32:
+            raise ValueError('%s: z1 and z2 are (N, D) fp32 matrices (got %s %s)' % (what, tuple(z.shape), z.dtype))
+    if z1.shape != z2.shape:
+        raise ValueError('%s: the two views differ in shape (%s, %s)' % (what, tuple(z1.shape), tuple(z2.shape)))
+    N, D = z1.shape
+    if N < 2 or N > 65536 or D < 1 or D > 8192 or N * D >= 2 ** 31:
+        raise ValueError('%s: 2 <= N <= 65536, 1 <= D <= 8192, N * D < 2^31 (got N=%d, D=%d)' % (what, N, D))
+    lambd, eps = float(lambd), float(eps)
+    if not 0.0 <= lambd < 3.0e38:
+        raise ValueError('%s: lambda must be non-negative and finite in fp32 (got %r)' % (what, lambd))
+    if not 0.0 <= eps < 3.0e38:
+        raise ValueError('%s: eps must be non-negative and finite in fp32 (got %r)' % (what, eps))
+    return N, D, lambd, eps
+
+
+def barlow_fwd(z1, z2, lambd, eps=1e-5):
+    """Barlow Twins forward (gca_barlow_fwd; tests/barlow_ref.py states the arithmetic): the (N, D) fp32 projector outputs of
+    the two views -> (loss3 = [loss, on, off], stats (4, D) = mean_1, rstd_1, mean_2, rstd_2, cmat (D, D), rsum (2, D)), all on
+    the device; stats, cmat and rsum are what barlow_bwd needs.  ValueError for arguments the kernel entry refuses."""
+    N, D, lambd, eps = _barlow_args(z1, z2, lambd, eps, 'barlow_fwd')
+    z1, z2 = z1.contiguous(), z2.contiguous()
+    p1, p2 = ptr(z1), ptr(z2)                                           # (RuntimeError for host tensors)
+    dev = z1.device
+    loss3 = torch.empty(3, dtype=F32, device=dev)
+    stats = torch.empty((4, D), dtype=F32, device=dev)
+    cmat = torch.empty((D, D), dtype=F32, device=dev)
+    rsum = torch.empty((2, D), dtype=F32, device=dev)
+    ws = WS.get(H.lib.gca_barlow_ws_bytes(N, D), dev)
+    H.call('gca_barlow_fwd', p1, p2, N, D, lambd, eps, ptr(stats), ptr(cmat), ptr(rsum), ptr(loss3), ptr(ws), stream())
+    return loss3, stats, cmat, rsum
+
+
+def barlow_bwd(z1, z2, stats, cmat, rsum, lambd, gscale_dev=None, gscale_host=1.0):
+    """d loss / d (z1, z2) of barlow_fwd from its saved state, times gscale_host * (*gscale_dev if given) -> (dz1, dz2)."""
+    N, D, lambd, _ = _barlow_args(z1, z2, lambd, 0.0, 'barlow_bwd')
+    gscale_host = float(gscale_host)
+    if not -3.0e38 < gscale_host < 3.0e38:
+        raise ValueError('barlow_bwd: gscale_host must be finite in fp32 (got %r)' % gscale_host)
+    for t, shape, name in ((stats, (4, D), 'stats'), (cmat, (D, D), 'cmat'), (rsum, (2, D), 'rsum')):
+        if t.dtype is not F32 or tuple(t.shape) != shape:
+            raise ValueError('barlow_bwd: %s is the %s fp32 tensor of barlow_fwd (got %s %s)' % (name, shape, tuple(t.shape), t.dtype))
+    z1, z2, stats, cmat, rsum = (t.contiguous() for t in (z1, z2, stats, cmat, rsum))
+    p1, p2 = ptr(z1), ptr(z2)
+    dz1 = torch.empty((N, D), dtype=F32, device=z1.device)
+    dz2 = torch.empty((N, D), dtype=F32, device=z1.device)
+    ws = WS.get(H.lib.gca_barlow_ws_bytes(N, D), z1.device)
+    H.call('gca_barlow_bwd', p1, p2, ptr(stats), ptr(cmat), ptr(rsum), N, D, lambd, ptr(gscale_dev), gscale_host, ptr(dz1),
+           ptr(dz2), ptr(ws), stream())
+    return dz1, dz2
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

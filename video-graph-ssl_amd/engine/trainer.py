@@ -1,4 +1,4 @@
-"""Pre-training step drivers (MoCo, SimSiam and SimCLR) on the HIP engine.
+"""Pre-training step drivers (MoCo, SimSiam, SimCLR and Barlow Twins) on the HIP engine.
 
 Restates the iteration of tools/train_video_contrast_dis.py:395-454 (_train_moco) and :479-523
 (_train_simsiam) without its host syncs (3x .item() per iteration, :429-431) and defects
@@ -638,6 +638,22 @@ class SimCLRTrainer(_TwoViewTrainer):
 
     def _outputs(self, lv):
         return dict(loss=lv.t, rank=self.model.model.rank)
+
+
+class BarlowTwinsTrainer(_TwoViewTrainer):
+    """Barlow Twins pre-training (CONTRAST.MEM_TYPE 'barlow', off-diagonal weight CONTRAST.BT_LAMBDA): SimSiamTrainer's step
+    with lib.modeling.graph_wrappers.BarlowTwins as the model.  `out` carries `loss` and its two sums `on_diag`, `off_diag`
+    (device scalars).  One GPU only: the column statistics and the cross-correlation over the global batch need all-reduces."""
+
+    def _check_cfg(self, cfg):
+        if cfg.CONTRAST.MEM_TYPE != 'barlow':
+            raise ValueError('BarlowTwinsTrainer needs CONTRAST.MEM_TYPE == barlow (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if self.ctx.active:
+            raise NotImplementedError('BarlowTwinsTrainer runs on one GPU: column statistics and the cross-correlation over the '
+                                      'global batch need all-reduces between the ranks')
+
+    def _outputs(self, lv):
+        return dict(loss=lv.t, on_diag=self.model.model.on_diag, off_diag=self.model.model.off_diag)
 
 
 class ActionTrainer(_TrainerBase):

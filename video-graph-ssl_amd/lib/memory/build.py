@@ -1,6 +1,7 @@
 """Factories (reference: lib/memory/build.py).  Only what the pre-training configs select is on the
-HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no memory, the loss module itself),
-CRITERION 'crossentropy'."""
+HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no memory, the loss module itself) /
+'barlow' (Barlow Twins' cross-correlation loss, likewise the loss module itself), CRITERION 'crossentropy'."""
+from .barlow import BarlowTwinsLoss
 from .criterion import NCESoftmaxLoss
 from .mem_moco import RGBMoCo
 from .ntxent import NTXent
@@ -15,6 +16,8 @@ def create_contrast(cfg, n_data):
         return None
     if cfg.CONTRAST.MEM_TYPE == 'simclr':
         return NTXent(cfg.CONTRAST.NCE_T)
+    if cfg.CONTRAST.MEM_TYPE == 'barlow':
+        return BarlowTwinsLoss(cfg.CONTRAST.BT_LAMBDA)
     raise NotImplementedError('mem not suported: {}'.format(cfg.CONTRAST.MEM_TYPE))
 
 

@@ -21,11 +21,11 @@ def create_video_model(cfg):
 
 
 def create_visual_model(cfg):
-    """-> (model, model_ema | None); only MoCo has a key encoder ('simsiam' and 'simclr' return None).  NOTE: the reference
-    never forwards MODEL.AUG_FLAG (dead code); here the flag is honoured so the graph block can actually be
+    """-> (model, model_ema | None); only MoCo has a key encoder ('simsiam', 'simclr' and 'barlow' return None).  NOTE: the
+    reference never forwards MODEL.AUG_FLAG (dead code); here the flag is honoured so the graph block can actually be
     switched on."""
     model = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE,
-                         nce_t=cfg.CONTRAST.NCE_T)
+                         nce_t=cfg.CONTRAST.NCE_T, bt_lambda=getattr(cfg.CONTRAST, 'BT_LAMBDA', 0.0051))
     model_ema = None
     if cfg.CONTRAST.MEM_TYPE == 'moco':
         model_ema = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE)

@@ -7,7 +7,7 @@ node (engine/autograd_bridge.py); the trainer's fused step calls ``fwd`` directl
 import torch
 import torch.nn as nn
 
-from .project_head import PredictionMLP, ProjectHead, ProjectionMLP
+from .project_head import BarlowProjector, PredictionMLP, ProjectHead, ProjectionMLP
 from ...engine import layers as L, ops
 from ...engine.autograd_bridge import run_module
 from ...engine.tape import Var
@@ -124,13 +124,59 @@ class SimCLR(ContrastWrapper):
         return run_module(self, x).reshape(())
 
 
+class BarlowTwins(nn.Module):
+    """Encoder + BarlowProjector trained with the Barlow Twins loss on the two views of a (b,6,T,H,W) batch (state dict:
+    ``encoder.*``, ``projection.*``, as SimSiam's without the predictor).  The views go through encoder + projector in TWO
+    passes, so BatchNorm statistics are per view, as in this package's SimSiam and SimCLR.  The loss is unscaled (the
+    original code multiplies it by a constant that LARS' trust ratio cancels)."""
+
+    def __init__(self, encoder, hid_dim=1024, lambd=0.0051, eps=1e-5):
+        super().__init__()
+        lambd = float(lambd)
+        if not 0.0 <= lambd < float('inf'):
+            raise ValueError('BarlowTwins: lambd must be non-negative and finite (got %r)' % lambd)
+        self.encoder = encoder
+        self.feature_dim = encoder.feature_dim
+        self.projection = BarlowProjector(self.feature_dim, hid_dim, hid_dim)
+        self.lambd, self.eps = lambd, float(eps)
+        self.on_diag = self.off_diag = None     # the two sums of the last forward (device scalars)
+
+    def fwd(self, tape, xv):
+        """loss = on + lambd * off of the views' cross-correlation, both views through the encoder WITH grad."""
+        x = xv.t
+        x1, x2 = torch.chunk(x, 2, dim=1)          # views, read in place through the batch stride
+        z1 = self.projection.fwd(tape, self.encoder.fwd(tape, Var(x1)))
+        z2 = self.projection.fwd(tape, self.encoder.fwd(tape, Var(x2)))
+        a, b = z1.t.contiguous(), z2.t.contiguous()
+        loss3, stats, cmat, rsum = ops.barlow_fwd(a, b, self.lambd, self.eps)
+        self.on_diag, self.off_diag = loss3[1:2], loss3[2:3]
+        lv = Var(loss3[:1], tape.recording)
+
+        def back():
+            # d loss / d (z1, z2) in one launch; the upstream scalar and the fp16-storage loss scale fold into its scale
+            g = lv.grad
+            gs = 1.0
+            if g is not None and g.numel() == 1 and not torch.cuda.is_current_stream_capturing():
+                gs = float(g.item())
+            dz1, dz2 = ops.barlow_bwd(a, b, stats, cmat, rsum, self.lambd, gscale_dev=ops.LOSS_SCALE_STATE[0], gscale_host=gs)
+            z1.add_grad(dz1)
+            z2.add_grad(dz2)
+        tape.record(back)
+        return lv
+
+    def forward(self, x):
+        return run_module(self, x).reshape(())
+
+
 class GraphWrapper(nn.Module):
-    def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07):
+    def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07, bt_lambda=0.0051):
         super().__init__()
         if mem_type == 'simsiam':
             self.model = SimSiam(encoder=encoder, hid_dim=hid_dim)
         elif mem_type == 'simclr':
             self.model = SimCLR(encoder=encoder, hid_dim=hid_dim, head_type=head_type, T=nce_t)
+        elif mem_type == 'barlow':
+            self.model = BarlowTwins(encoder=encoder, hid_dim=hid_dim, lambd=bt_lambda)
         else:
             self.model = ContrastWrapper(encoder=encoder, hid_dim=hid_dim, head_type=head_type)
 

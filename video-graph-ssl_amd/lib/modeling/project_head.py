@@ -50,6 +50,20 @@ class ProjectionMLP(nn.Module):
         return _lin_bn(tape, self.l3, _lin_bn(tape, self.l2, _lin_bn(tape, self.l1, xv)))
 
 
+class BarlowProjector(nn.Module):
+    """Barlow Twins' projector: ProjectionMLP's l1 / l2 and a bare last Linear -- the loss standardises every output column
+    over the batch, which cancels a bias and a BatchNorm there (not in the reference)."""
+
+    def __init__(self, in_dim, hid_dim, out_dim):
+        super().__init__()
+        self.l1 = nn.Sequential(HipLinear(in_dim, hid_dim), HipBatchNorm1d(hid_dim), HipReLU(inplace=True))
+        self.l2 = nn.Sequential(HipLinear(hid_dim, hid_dim), HipBatchNorm1d(hid_dim), HipReLU(inplace=True))
+        self.l3 = HipLinear(hid_dim, out_dim, bias=False)
+
+    def fwd(self, tape, xv):
+        return L.f_linear(tape, self.l3, _lin_bn(tape, self.l2, _lin_bn(tape, self.l1, xv)))
+
+
 class PredictionMLP(nn.Module):
     def __init__(self, in_dim, hid_dim, out_dim):
         super().__init__()
