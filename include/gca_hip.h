@@ -597,6 +597,35 @@ int gca_barlow_bwd(const float* z1, const float* z2, const float* stats, const f
                    void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * VICReg: the variance / invariance / covariance loss of two views and its gradient (csrc/vicreg.hip).  Not in the reference;
+ * like Barlow Twins it needs no negatives, queue, momentum encoder or predictor, and it does not standardise the features.
+ * z1, z2 (N, D) fp32 contiguous: the projector outputs of view 1 / view 2 of the same N clips.  Per view v (x = z_v), in two passes:
+ *   mean_v[d] = (sum_n x[n,d]) / N        xc = x - mean_v       var_v[d] = (sum_n xc[n,d]^2) / (N - 1)    (unbiased)
+ *   sd_v[d]   = sqrt(var_v[d] + eps)                            Cov_v[i,j] = (sum_n xc[n,i] xc[n,j]) / (N - 1)
+ *   inv  = sum_{n,d} (z1 - z2)^2 / (N D)      varl = sum_v sum_d max(0, 1 - sd_v[d]) / (2 D)      covl = sum_v sum_{i != j} Cov_v[i,j]^2 / D
+ *   loss = sim * inv + std * varl + cov * covl
+ *   dz_v[n,j] = g * (s_v * 2 sim (z1 - z2)[n,j] / (N D) - std * [sd_v[j] < 1] * xc[n,j] / (2 D sd_v[j] (N - 1))
+ *                    + 4 cov / (D (N - 1)) * sum_{i != j} xc[n,i] Cov_v[i,j]),      s_1 = +1, s_2 = -1,
+ *   g = gscale_host * (gscale_dev ? *gscale_dev : 1), as in gca_barlow_bwd.  The centring adds no term to the gradient.
+ * Saved state, caller-owned, written by the forward and read by the backward: stats (4, D) = mean_1, sd_1, mean_2, sd_2;
+ * covm (2, D, D) = Cov_1, Cov_2 (diagonals included), 8 D^2 bytes.  loss4[4] = loss, inv, varl, covl (the parts unweighted).
+ * `ws`: gca_vicreg_ws_bytes(N, D) bytes (always > 0 for valid sizes) of scratch of the forward; the backward uses none of it.
+ * Products on v_mfma_f32_32x32x2_f32 (exact fp32, fp32 accumulation).  Cov is symmetric: only the 64 x 64 tiles on and above
+ * the diagonal are computed, and each off-diagonal one is written twice.  No atomics: outputs are bitwise the same from call
+ * to call.  No host sync, allocation or read: both entries can be captured in a hipGraph.  Launches: forward 3 (column
+ * statistics with the hinge and invariance partials; Cov tiles with their square-sums; the fold in fp64), backward 1 (both
+ * views).  One dispatch path (guarded 4-byte accesses, no alignment assumed).  tests/vicreg_ref.py restates the arithmetic.
+ * eps == 0 with a constant column gives sd = 0 and 0 / 0 = NaN in that column's gradient, as the chain of torch ops does: the
+ * caller's business, not a refusal.
+ * GCA_EINVAL (nothing launched, nothing written; -1 from gca_vicreg_ws_bytes) for N < 2, N > 65536, D < 1, D > 8192,
+ * N * D >= 2^31, sim, std, cov or eps negative or not finite, gscale_host not finite, any NULL pointer other than gscale_dev. */
+int64_t gca_vicreg_ws_bytes(int64_t N, int64_t D);
+int gca_vicreg_fwd(const float* z1, const float* z2, int64_t N, int64_t D, float sim, float std, float cov, float eps, float* stats,
+                   float* covm, float* loss4, void* ws, void* stream);
+int gca_vicreg_bwd(const float* z1, const float* z2, const float* stats, const float* covm, int64_t N, int64_t D, float sim,
+                   float std, float cov, const float* gscale_dev, float gscale_host, float* dz1, float* dz2, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

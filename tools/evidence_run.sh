@@ -19,4 +19,5 @@ cp $(ls gpurun_out/pmc_step/trace/*kernel_stats.csv | head -1) $E/f16_bench_kern
 rm -rf gpurun_out/pmc_step; echo f16 pmc done
 bash tools/pmc_conv.sh L00,L01,L02 wgrad > $E/sq_counters_wgrad.txt 2>&1 || echo pmc_conv failed
 rm -rf gpurun_out/pmc_conv
+timeout -k 10 600 python tools/vicreg_micro.py --out $E/vicreg_micro.json > $E/vicreg_micro.log 2>&1 || { echo vicreg_micro failed; tail -5 $E/vicreg_micro.log; }
 ls -la $E

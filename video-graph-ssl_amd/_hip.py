@@ -147,6 +147,9 @@ SIGNATURES = {
     'gca_barlow_ws_bytes': (c_i64, [c_i64, c_i64]),
     'gca_barlow_fwd': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'gca_barlow_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    'gca_vicreg_ws_bytes': (c_i64, [c_i64, c_i64]),
+    'gca_vicreg_fwd': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'gca_vicreg_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
     'gca_classifier_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_classifier_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'gca_classifier_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32,

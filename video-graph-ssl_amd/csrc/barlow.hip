@@ -25,31 +25,10 @@
 // path: every global access is a guarded 4-byte one with lanes along D, so no alignment or divisibility is assumed.
 #include <cstdint>
 #include "gca_common.h"
+#include "mma_tile.h"
 #include <math.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
-
-constexpr int KC = 32;               // reduction elements per staged chunk
-constexpr int TW = 64;               // output tile edge of a workgroup
-constexpr int TP = TW + 1;           // LDS pitch of a [k][64] chunk: the transposed staging writes with stride TP
-constexpr int NPT = KC * TW / 256;   // elements of a chunk per thread
-constexpr int FLUSH = 2048;          // rows of N after which the forward moves its accumulator tile into a second one
-
-__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-__device__ __forceinline__ float half_sum(float v) {         // over the 32 lanes of a wave half, valid in every lane
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// acc[A index][B index] += sum_k As[k][arow + .] Bs[k][bcol + .] over one chunk
-__device__ __forceinline__ void chunk_mma(f32x16& acc, const float* As, const float* Bs, int arow, int bcol, int ll, int lh) {
-#pragma unroll
-  for (int k = 0; k < KC; k += 2)
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(k + lh) * TP + arow + ll], Bs[(k + lh) * TP + bcol + ll], acc, 0, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------------------ forward
 __global__ __launch_bounds__(256) void barlow_stats_kernel(const float* __restrict__ z1, const float* __restrict__ z2, int N, int D,

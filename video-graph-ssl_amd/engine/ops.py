@@ -993,6 +993,62 @@ def barlow_bwd(z1, z2, stats, cmat, rsum, lambd, gscale_dev=None, gscale_host=1.
     return dz1, dz2
 
 
+# ----------------------------------------------------------------------------- VICReg
+def _vicreg_args(z1, z2, sim, std, cov, eps, what):
+    """Host-side refusals of gca_vicreg_fwd / _bwd (before any device is touched) -> (N, D, sim, std, cov, eps)."""
+    for z in (z1, z2):
+        if z.dim() != 2 or z.dtype is not F32:
+            raise ValueError('%s: z1 and z2 are (N, D) fp32 matrices (got %s %s)' % (what, tuple(z.shape), z.dtype))
+    if z1.shape != z2.shape:
+        raise ValueError('%s: the two views differ in shape (%s, %s)' % (what, tuple(z1.shape), tuple(z2.shape)))
+    N, D = z1.shape
+    if N < 2 or N > 65536 or D < 1 or D > 8192 or N * D >= 2 ** 31:
+        raise ValueError('%s: 2 <= N <= 65536, 1 <= D <= 8192, N * D < 2^31 (got N=%d, D=%d)' % (what, N, D))
+    vals = []
+    for name, v in (('sim', sim), ('std', std), ('cov', cov), ('eps', eps)):
+        v = float(v)
+        if not 0.0 <= v < 3.0e38:
+            raise ValueError('%s: %s must be non-negative and finite in fp32 (got %r)' % (what, name, v))
+        vals.append(v)
+    return (N, D) + tuple(vals)
+
+
+def vicreg_fwd(z1, z2, sim, std, cov, eps=1e-4):
+    """VICReg forward (gca_vicreg_fwd; tests/vicreg_ref.py states the arithmetic): the (N, D) fp32 projector outputs of the two
+    views -> (loss4 = [loss, inv, varl, covl] with the parts unweighted, stats (4, D) = mean_1, sd_1, mean_2, sd_2, covm
+    (2, D, D), 8 D^2 bytes), all on the device; stats and covm are what vicreg_bwd needs.  ValueError for arguments the kernel
+    entry refuses."""
+    N, D, sim, std, cov, eps = _vicreg_args(z1, z2, sim, std, cov, eps, 'vicreg_fwd')
+    z1, z2 = z1.contiguous(), z2.contiguous()
+    p1, p2 = ptr(z1), ptr(z2)                                           # (RuntimeError for host tensors)
+    dev = z1.device
+    loss4 = torch.empty(4, dtype=F32, device=dev)
+    stats = torch.empty((4, D), dtype=F32, device=dev)
+    covm = torch.empty((2, D, D), dtype=F32, device=dev)
+    ws = WS.get(H.lib.gca_vicreg_ws_bytes(N, D), dev)
+    H.call('gca_vicreg_fwd', p1, p2, N, D, sim, std, cov, eps, ptr(stats), ptr(covm), ptr(loss4), ptr(ws), stream())
+    return loss4, stats, covm
+
+
+def vicreg_bwd(z1, z2, stats, covm, sim, std, cov, gscale_dev=None, gscale_host=1.0):
+    """d loss / d (z1, z2) of vicreg_fwd from its saved state, times gscale_host * (*gscale_dev if given) -> (dz1, dz2)."""
+    N, D, sim, std, cov, _ = _vicreg_args(z1, z2, sim, std, cov, 0.0, 'vicreg_bwd')
+    gscale_host = float(gscale_host)
+    if not -3.0e38 < gscale_host < 3.0e38:
+        raise ValueError('vicreg_bwd: gscale_host must be finite in fp32 (got %r)' % gscale_host)
+    for t, shape, name in ((stats, (4, D), 'stats'), (covm, (2, D, D), 'covm')):
+        if t.dtype is not F32 or tuple(t.shape) != shape:
+            raise ValueError('vicreg_bwd: %s is the %s fp32 tensor of vicreg_fwd (got %s %s)' % (name, shape, tuple(t.shape), t.dtype))
+    z1, z2, stats, covm = (t.contiguous() for t in (z1, z2, stats, covm))
+    p1, p2 = ptr(z1), ptr(z2)
+    dz1 = torch.empty((N, D), dtype=F32, device=z1.device)
+    dz2 = torch.empty((N, D), dtype=F32, device=z1.device)
+    ws = WS.get(H.lib.gca_vicreg_ws_bytes(N, D), z1.device)
+    H.call('gca_vicreg_bwd', p1, p2, ptr(stats), ptr(covm), N, D, sim, std, cov, ptr(gscale_dev), gscale_host, ptr(dz1), ptr(dz2),
+           ptr(ws), stream())
+    return dz1, dz2
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

@@ -1,4 +1,4 @@
-"""Pre-training step drivers (MoCo, SimSiam, SimCLR and Barlow Twins) on the HIP engine.
+"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins and VICReg) on the HIP engine.
 
 Restates the iteration of tools/train_video_contrast_dis.py:395-454 (_train_moco) and :479-523
 (_train_simsiam) without its host syncs (3x .item() per iteration, :429-431) and defects
@@ -654,6 +654,24 @@ class BarlowTwinsTrainer(_TwoViewTrainer):
 
     def _outputs(self, lv):
         return dict(loss=lv.t, on_diag=self.model.model.on_diag, off_diag=self.model.model.off_diag)
+
+
+class VICRegTrainer(_TwoViewTrainer):
+    """VICReg pre-training (CONTRAST.MEM_TYPE 'vicreg', weights CONTRAST.VIC_SIM / VIC_STD / VIC_COV): SimSiamTrainer's step with
+    lib.modeling.graph_wrappers.VICReg as the model.  `out` carries `loss` and its three unweighted parts `inv`, `var`, `cov`
+    (device scalars).  One GPU only: the column statistics and the covariances over the global batch need a feature
+    all-gather between the ranks."""
+
+    def _check_cfg(self, cfg):
+        if cfg.CONTRAST.MEM_TYPE != 'vicreg':
+            raise ValueError('VICRegTrainer needs CONTRAST.MEM_TYPE == vicreg (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if self.ctx.active:
+            raise NotImplementedError('VICRegTrainer runs on one GPU: column statistics and covariances over the global batch '
+                                      'need a feature all-gather between the ranks')
+
+    def _outputs(self, lv):
+        m = self.model.model
+        return dict(loss=lv.t, inv=m.inv, var=m.var, cov=m.cov)
 
 
 class ActionTrainer(_TrainerBase):

@@ -1,10 +1,12 @@
 """Factories (reference: lib/memory/build.py).  Only what the pre-training configs select is on the
 HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no memory, the loss module itself) /
-'barlow' (Barlow Twins' cross-correlation loss, likewise the loss module itself), CRITERION 'crossentropy'."""
+'barlow' (Barlow Twins' cross-correlation loss, likewise the loss module itself) / 'vicreg' (the variance / invariance /
+covariance loss, likewise), CRITERION 'crossentropy'."""
 from .barlow import BarlowTwinsLoss
 from .criterion import NCESoftmaxLoss
 from .mem_moco import RGBMoCo
 from .ntxent import NTXent
+from .vicreg import VICRegLoss
 
 
 def create_contrast(cfg, n_data):
@@ -18,6 +20,8 @@ def create_contrast(cfg, n_data):
         return NTXent(cfg.CONTRAST.NCE_T)
     if cfg.CONTRAST.MEM_TYPE == 'barlow':
         return BarlowTwinsLoss(cfg.CONTRAST.BT_LAMBDA)
+    if cfg.CONTRAST.MEM_TYPE == 'vicreg':
+        return VICRegLoss(cfg.CONTRAST.VIC_SIM, cfg.CONTRAST.VIC_STD, cfg.CONTRAST.VIC_COV)
     raise NotImplementedError('mem not suported: {}'.format(cfg.CONTRAST.MEM_TYPE))
 
 

@@ -11,6 +11,7 @@ from .project_head import BarlowProjector, PredictionMLP, ProjectHead, Projectio
 from ...engine import layers as L, ops
 from ...engine.autograd_bridge import run_module
 from ...engine.tape import Var
+from ..memory.vicreg import check_coeffs
 
 
 class ContrastWrapper(nn.Module):
@@ -124,6 +125,32 @@ class SimCLR(ContrastWrapper):
         return run_module(self, x).reshape(())
 
 
+def _two_view_loss(model, tape, xv, loss_fwd, loss_bwd, fwd_args, bwd_args):
+    """The step that BarlowTwins and VICReg share: both views of a (b,6,T,H,W) batch through model.encoder + model.projection
+    in two passes, then one fused loss pair of engine.ops on the two (N, D) feature matrices: ``loss_fwd(z1, z2, *fwd_args) ->
+    (parts, *saved)`` with the loss in parts[0], and on the way back ``loss_bwd(z1, z2, *saved, *bwd_args, gscale_dev,
+    gscale_host) -> (dz1, dz2)``.  -> (the loss Var, parts)."""
+    x = xv.t
+    x1, x2 = torch.chunk(x, 2, dim=1)          # views, read in place through the batch stride
+    z1 = model.projection.fwd(tape, model.encoder.fwd(tape, Var(x1)))
+    z2 = model.projection.fwd(tape, model.encoder.fwd(tape, Var(x2)))
+    a, b = z1.t.contiguous(), z2.t.contiguous()
+    parts, *saved = loss_fwd(a, b, *fwd_args)
+    lv = Var(parts[:1], tape.recording)
+
+    def back():
+        # d loss / d (z1, z2) in one launch; the upstream scalar and the fp16-storage loss scale fold into its scale
+        g = lv.grad
+        gs = 1.0
+        if g is not None and g.numel() == 1 and not torch.cuda.is_current_stream_capturing():
+            gs = float(g.item())
+        dz1, dz2 = loss_bwd(a, b, *saved, *bwd_args, gscale_dev=ops.LOSS_SCALE_STATE[0], gscale_host=gs)
+        z1.add_grad(dz1)
+        z2.add_grad(dz2)
+    tape.record(back)
+    return lv, parts
+
+
 class BarlowTwins(nn.Module):
     """Encoder + BarlowProjector trained with the Barlow Twins loss on the two views of a (b,6,T,H,W) batch (state dict:
     ``encoder.*``, ``projection.*``, as SimSiam's without the predictor).  The views go through encoder + projector in TWO
@@ -143,25 +170,34 @@ class BarlowTwins(nn.Module):
 
     def fwd(self, tape, xv):
         """loss = on + lambd * off of the views' cross-correlation, both views through the encoder WITH grad."""
-        x = xv.t
-        x1, x2 = torch.chunk(x, 2, dim=1)          # views, read in place through the batch stride
-        z1 = self.projection.fwd(tape, self.encoder.fwd(tape, Var(x1)))
-        z2 = self.projection.fwd(tape, self.encoder.fwd(tape, Var(x2)))
-        a, b = z1.t.contiguous(), z2.t.contiguous()
-        loss3, stats, cmat, rsum = ops.barlow_fwd(a, b, self.lambd, self.eps)
+        lv, loss3 = _two_view_loss(self, tape, xv, ops.barlow_fwd, ops.barlow_bwd, (self.lambd, self.eps), (self.lambd,))
         self.on_diag, self.off_diag = loss3[1:2], loss3[2:3]
-        lv = Var(loss3[:1], tape.recording)
+        return lv
 
-        def back():
-            # d loss / d (z1, z2) in one launch; the upstream scalar and the fp16-storage loss scale fold into its scale
-            g = lv.grad
-            gs = 1.0
-            if g is not None and g.numel() == 1 and not torch.cuda.is_current_stream_capturing():
-                gs = float(g.item())
-            dz1, dz2 = ops.barlow_bwd(a, b, stats, cmat, rsum, self.lambd, gscale_dev=ops.LOSS_SCALE_STATE[0], gscale_host=gs)
-            z1.add_grad(dz1)
-            z2.add_grad(dz2)
-        tape.record(back)
+    def forward(self, x):
+        return run_module(self, x).reshape(())
+
+
+class VICReg(nn.Module):
+    """Encoder + expander trained with the VICReg loss on the two views of a (b,6,T,H,W) batch (state dict: ``encoder.*``,
+    ``projection.*``).  VICReg's expander -- two Linear-BN-ReLU layers and a bare last Linear -- is BarlowProjector.  The views
+    go through encoder + expander in TWO passes, so BatchNorm statistics are per view, as in this package's other two-view
+    objectives."""
+
+    def __init__(self, encoder, hid_dim=1024, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, eps=1e-4):
+        super().__init__()
+        self.sim_coeff, self.std_coeff, self.cov_coeff, self.eps = check_coeffs(
+            'VICReg', sim_coeff=sim_coeff, std_coeff=std_coeff, cov_coeff=cov_coeff, eps=eps)
+        self.encoder = encoder
+        self.feature_dim = encoder.feature_dim
+        self.projection = BarlowProjector(self.feature_dim, hid_dim, hid_dim)
+        self.inv = self.var = self.cov = None   # the three unweighted parts of the last forward (device scalars)
+
+    def fwd(self, tape, xv):
+        """loss = sim inv + std varl + cov covl of the two views' features, both views through the encoder WITH grad."""
+        coeffs = (self.sim_coeff, self.std_coeff, self.cov_coeff)
+        lv, loss4 = _two_view_loss(self, tape, xv, ops.vicreg_fwd, ops.vicreg_bwd, coeffs + (self.eps,), coeffs)
+        self.inv, self.var, self.cov = loss4[1:2], loss4[2:3], loss4[3:4]
         return lv
 
     def forward(self, x):
@@ -169,7 +205,8 @@ class BarlowTwins(nn.Module):
 
 
 class GraphWrapper(nn.Module):
-    def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07, bt_lambda=0.0051):
+    def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07, bt_lambda=0.0051,
+                 vic_coeffs=(25.0, 25.0, 1.0)):
         super().__init__()
         if mem_type == 'simsiam':
             self.model = SimSiam(encoder=encoder, hid_dim=hid_dim)
@@ -177,6 +214,8 @@ class GraphWrapper(nn.Module):
             self.model = SimCLR(encoder=encoder, hid_dim=hid_dim, head_type=head_type, T=nce_t)
         elif mem_type == 'barlow':
             self.model = BarlowTwins(encoder=encoder, hid_dim=hid_dim, lambd=bt_lambda)
+        elif mem_type == 'vicreg':
+            self.model = VICReg(encoder, hid_dim, *vic_coeffs)
         else:
             self.model = ContrastWrapper(encoder=encoder, hid_dim=hid_dim, head_type=head_type)
 
