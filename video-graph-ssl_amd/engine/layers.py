@@ -229,8 +229,11 @@ BN_SMALL_ELEMS = 32768      # bn.hip: N*SP at or below this runs finalize + appl
 def _conv_input(conv, xv):
     """-> (plan, x, xf): what a conv reads.  A LazyVar producer (conv -> BN -> ReLU not yet written) is consumed as (y, (scale,
     shift)) when this conv's pinned launch shapes can apply the BatchNorm + ReLU while staging (ops.conv_xf_ok: forward on an
-    LDS-halo kernel, weight gradient on a streaming kernel; resnet2p1d.py:66-85's bn1_s -> conv1_t, bn1_t -> conv2_s,
-    bn2_s -> conv2_t and the stem, s3d_1.py:61-68's conv_s -> conv_t); otherwise its `.t` materialises z."""
+    LDS-halo kernel AND weight gradient on a TEMPORAL streaming kernel, temporal32 / temporal64 -- the (k,1,1) consumers:
+    resnet2p1d.py:66-85's bn1_s -> conv1_t and bn2_s -> conv2_t, s3d_1.py:61-68's conv_s -> conv_t).  Every other consumer
+    reads `.t`, which materialises z: a (1,k,k) conv even with the spatial streaming weight-gradient kernel pinned (bn1_t ->
+    conv2_s), the stem kernels, pools, and every conv under fp32 MFMA arithmetic or fp16 storage
+    (tests/test_units_ref.py pins these selections on the host)."""
     if isinstance(xv, LazyVar) and not xv.materialized and LAZY_BN:
         plan = conv.plan(xv.y)
         if ops.conv_xf_ok(plan):
