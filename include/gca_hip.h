@@ -626,6 +626,41 @@ int gca_vicreg_bwd(const float* z1, const float* z2, const float* stats, const f
                    float std, float cov, const float* gscale_dev, float gscale_host, float* dz1, float* dz2, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * SwAV: Sinkhorn-Knopp codes, the swapped-prediction loss of two views against learned prototypes, and its gradient
+ * (csrc/swav.hip; Caron et al. 2020).  Not in the reference.  z1, z2 (N, D) and the prototypes C (K, D), fp32 contiguous, all
+ * with unit rows (a precondition, not checked on the device).  Per view v:
+ *   S_v = z_v C^T (N, K)                         P_v = exp((S_v - 1) / eps)      (the codes do not depend on the constant)
+ *   u_v[k] = 1 / (K sum_n P_v[n,k] v_v[n])       v_v[n] = 1 / (N sum_k P_v[n,k] u_v[k])     `iters` times, v_v = 1 at first
+ *   q_v[n,k] = N P_v[n,k] u_v[k] v_v[n]          the Sinkhorn-Knopp loop of the paper as two scaling vectors; no gradient
+ *   lse_v[n] = log sum_k exp(S_v[n,k] / T)       l12 = -(1/N) sum_{n,k} q_2 (S_1 / T - lse_1)     l21 with 1 <-> 2
+ *   loss = (l12 + l21) / 2                       dS_1 = (exp(S_1 / T - lse_1) - q_2) / (2 N T)    dS_2 with 1 <-> 2
+ *   dz_v = g dS_v C       dC (+)= g (dS_1^T z_1 + dS_2^T z_2)       g = gscale_host * (gscale_dev ? *gscale_dev : 1)
+ * parts[3] = loss, l12, l21.  Saved state, caller-owned, written by the forward and read by the backward: dS (2, N, K), 8 N K
+ * bytes (it holds the scores until the last forward launch replaces them in place).  codes: NULL, or (2, N, K) that receives
+ * q_1, q_2 (tests and monitoring).  `ws`: gca_swav_ws_bytes(N, D, K) bytes (> 0 for valid sizes) of scratch, enough for either
+ * entry; nothing in it passes from the forward to the backward.
+ * Products on v_mfma_f32_32x32x2_f32 (exact fp32, fp32 accumulation), 64 x 64 tiles, all edges guarded.  Launches: forward
+ * 2 iters + 2 (scores; column sums and row sums alternately, both views per grid; the last row sums with codes, loss terms and
+ * dS; the fold in fp64), backward 2 or 3 (dz of both views, its reduction over K cut into gca_swav_dz_splits(N, D, K) slabs --
+ * min(32, max(1, 256 / (2 ceil(N / 64) ceil(D / 64))), ceil(K / 256)) -- whose partial tiles a second launch adds in slab
+ * order when there is more than one; dC over the 2 N rows, view 1 first).  No atomics: outputs are bitwise
+ * the same from call to call.  No host sync, allocation or read: every entry can be captured in a hipGraph.  One dispatch
+ * path, 4-byte accesses only.  tests/swav_ref.py restates the arithmetic.
+ * GCA_EINVAL (nothing launched, nothing written; -1 from gca_swav_ws_bytes) for N outside [2, 8192], K outside [2, 65536],
+ * D outside [1, 8192], iters outside [1, 16], eps outside [0.025, 1] (exp(-2 / eps) stays a normal fp32 number), T not
+ * positive or T or 1 / T not finite in fp32, gscale_host not finite, any NULL pointer other than codes and gscale_dev.
+ * gca_rows_normalize: C[k,:] /= ||C[k,:]|| in place, one wave per row, an all-zero row left as it is; GCA_EINVAL for NULL,
+ * K outside [1, 65536], D outside [1, 8192]. */
+int gca_rows_normalize(float* C, int64_t K, int64_t D, void* stream);
+int64_t gca_swav_ws_bytes(int64_t N, int64_t D, int64_t K);
+int gca_swav_fwd(const float* z1, const float* z2, const float* C, int64_t N, int64_t D, int64_t K, float eps, float T, int64_t iters,
+                 float* parts, float* dS, float* codes, void* ws, void* stream);
+int gca_swav_dz_splits(int64_t N, int64_t D, int64_t K);
+int gca_swav_bwd(const float* z1, const float* z2, const float* C, const float* dS, int64_t N, int64_t D, int64_t K,
+                 const float* gscale_dev, float gscale_host, float* dz1, float* dz2, float* dC, int accumulate_dC, void* ws,
+                 void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

@@ -20,4 +20,5 @@ rm -rf gpurun_out/pmc_step; echo f16 pmc done
 bash tools/pmc_conv.sh L00,L01,L02 wgrad > $E/sq_counters_wgrad.txt 2>&1 || echo pmc_conv failed
 rm -rf gpurun_out/pmc_conv
 timeout -k 10 600 python tools/vicreg_micro.py --out $E/vicreg_micro.json > $E/vicreg_micro.log 2>&1 || { echo vicreg_micro failed; tail -5 $E/vicreg_micro.log; }
+timeout -k 10 600 python tools/swav_micro.py --out $E/swav_micro.json > $E/swav_micro.log 2>&1 || { echo swav_micro failed; tail -5 $E/swav_micro.log; }
 ls -la $E

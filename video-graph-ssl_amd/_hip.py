@@ -150,6 +150,11 @@ SIGNATURES = {
     'gca_vicreg_ws_bytes': (c_i64, [c_i64, c_i64]),
     'gca_vicreg_fwd': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'gca_vicreg_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    'gca_rows_normalize': (c_i32, [c_vp, c_i64, c_i64, c_vp]),
+    'gca_swav_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
+    'gca_swav_fwd': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'gca_swav_dz_splits': (c_i32, [c_i64, c_i64, c_i64]),
+    'gca_swav_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     'gca_classifier_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_classifier_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'gca_classifier_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32,

@@ -1049,6 +1049,90 @@ def vicreg_bwd(z1, z2, stats, covm, sim, std, cov, gscale_dev=None, gscale_host=
     return dz1, dz2
 
 
+# ----------------------------------------------------------------------------- SwAV
+def rows_normalize_(C):
+    """C[k,:] /= ||C[k,:]|| in place (gca_rows_normalize): C (K, D) fp32 contiguous on the device, 1 <= K <= 65536,
+    1 <= D <= 8192; an all-zero row is left as it is.  -> C."""
+    if C.dim() != 2 or C.dtype is not F32 or not C.is_contiguous():
+        raise ValueError('rows_normalize_: C is a contiguous (K, D) fp32 matrix (got %s %s)' % (tuple(C.shape), C.dtype))
+    K, D = C.shape
+    if not (1 <= K <= 65536 and 1 <= D <= 8192):
+        raise ValueError('rows_normalize_: 1 <= K <= 65536, 1 <= D <= 8192 (got K=%d, D=%d)' % (K, D))
+    H.call('gca_rows_normalize', ptr(C), K, D, stream())
+    return C
+
+
+def _swav_args(z1, z2, C, what):
+    """Host-side refusals of gca_swav_fwd / _bwd on the shapes (before any device is touched) -> (N, D, K)."""
+    for z in (z1, z2):
+        if z.dim() != 2 or z.dtype is not F32:
+            raise ValueError('%s: z1 and z2 are (N, D) fp32 matrices (got %s %s)' % (what, tuple(z.shape), z.dtype))
+    if z1.shape != z2.shape:
+        raise ValueError('%s: the two views differ in shape (%s, %s)' % (what, tuple(z1.shape), tuple(z2.shape)))
+    N, D = z1.shape
+    if C.dim() != 2 or C.dtype is not F32 or C.shape[1] != D:
+        raise ValueError('%s: the prototypes C are a (K, D) fp32 matrix with D = %d (got %s %s)' % (what, D, tuple(C.shape), C.dtype))
+    K = C.shape[0]
+    if not (2 <= N <= 8192 and 2 <= K <= 65536 and 1 <= D <= 8192):
+        raise ValueError('%s: 2 <= N <= 8192, 2 <= K <= 65536, 1 <= D <= 8192 (got N=%d, K=%d, D=%d)' % (what, N, K, D))
+    return N, D, K
+
+
+def swav_params(what, eps, T, iters):
+    """-> (eps, T, iters) as gca_swav_fwd accepts them; ValueError otherwise (0.025 <= eps <= 1, T > 0 with T and 1 / T finite
+    in fp32, 1 <= iters <= 16)."""
+    import ctypes
+    eps, T = float(eps), float(T)
+    if isinstance(iters, bool) or int(iters) != iters:
+        raise ValueError('%s: iters is an integer (got %r)' % (what, iters))
+    iters = int(iters)
+    if not ctypes.c_float(0.025).value <= ctypes.c_float(eps).value <= 1.0:
+        raise ValueError('%s: eps must lie in [0.025, 1] (got %r)' % (what, eps))
+    if not 1.2e-38 < T < 3.0e38:
+        raise ValueError('%s: T must be positive, T and 1 / T finite in fp32 (got %r)' % (what, T))
+    if not 1 <= iters <= 16:
+        raise ValueError('%s: iters must lie in [1, 16] (got %r)' % (what, iters))
+    return eps, T, iters
+
+
+def swav_fwd(z1, z2, C, eps, T, iters, want_codes=False):
+    """SwAV forward (gca_swav_fwd; tests/swav_ref.py states the arithmetic): the (N, D) fp32 unit-row features of the two views
+    and the (K, D) unit-row prototypes -> (parts = [loss, l12, l21], dS (2, N, K)[, codes (2, N, K)]), all on the device.  dS,
+    8 N K bytes, is d loss / d (S_1, S_2) and all that swav_bwd needs.  ValueError for arguments the kernel entry refuses."""
+    N, D, K = _swav_args(z1, z2, C, 'swav_fwd')
+    eps, T, iters = swav_params('swav_fwd', eps, T, iters)
+    z1, z2, C = z1.contiguous(), z2.contiguous(), C.contiguous()
+    p1, p2, pc = ptr(z1), ptr(z2), ptr(C)                               # (RuntimeError for host tensors)
+    dev = z1.device
+    parts = torch.empty(3, dtype=F32, device=dev)
+    dS = torch.empty((2, N, K), dtype=F32, device=dev)
+    codes = torch.empty((2, N, K), dtype=F32, device=dev) if want_codes else None
+    ws = WS.get(H.lib.gca_swav_ws_bytes(N, D, K), dev)
+    H.call('gca_swav_fwd', p1, p2, pc, N, D, K, eps, T, iters, ptr(parts), ptr(dS), ptr(codes), ptr(ws), stream())
+    return (parts, dS, codes) if want_codes else (parts, dS)
+
+
+def swav_bwd(z1, z2, C, dS, dC, accumulate, gscale_dev=None, gscale_host=1.0):
+    """d loss / d (z1, z2) of swav_fwd from its saved dS, times gscale_host * (*gscale_dev if given) -> (dz1, dz2); the
+    prototypes' gradient, scaled alike, goes into dC (K, D) (added to it with `accumulate`)."""
+    N, D, K = _swav_args(z1, z2, C, 'swav_bwd')
+    gscale_host = float(gscale_host)
+    if not -3.0e38 < gscale_host < 3.0e38:
+        raise ValueError('swav_bwd: gscale_host must be finite in fp32 (got %r)' % gscale_host)
+    if dS.dtype is not F32 or tuple(dS.shape) != (2, N, K):
+        raise ValueError('swav_bwd: dS is the (2, %d, %d) fp32 tensor of swav_fwd (got %s %s)' % (N, K, tuple(dS.shape), dS.dtype))
+    if dC.dtype is not F32 or tuple(dC.shape) != (K, D) or not dC.is_contiguous():
+        raise ValueError('swav_bwd: dC is a contiguous (%d, %d) fp32 matrix (got %s %s)' % (K, D, tuple(dC.shape), dC.dtype))
+    z1, z2, C, dS = (t.contiguous() for t in (z1, z2, C, dS))
+    p1, p2, pc = ptr(z1), ptr(z2), ptr(C)
+    dz1 = torch.empty((N, D), dtype=F32, device=z1.device)
+    dz2 = torch.empty((N, D), dtype=F32, device=z1.device)
+    ws = WS.get(H.lib.gca_swav_ws_bytes(N, D, K), z1.device)
+    H.call('gca_swav_bwd', p1, p2, pc, ptr(dS), N, D, K, ptr(gscale_dev), gscale_host, ptr(dz1), ptr(dz2), ptr(dC),
+           int(bool(accumulate)), ptr(ws), stream())
+    return dz1, dz2
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

@@ -1,4 +1,4 @@
-"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins and VICReg) on the HIP engine.
+"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins, VICReg and SwAV) on the HIP engine.
 
 Restates the iteration of tools/train_video_contrast_dis.py:395-454 (_train_moco) and :479-523
 (_train_simsiam) without its host syncs (3x .item() per iteration, :429-431) and defects
@@ -672,6 +672,24 @@ class VICRegTrainer(_TwoViewTrainer):
     def _outputs(self, lv):
         m = self.model.model
         return dict(loss=lv.t, inv=m.inv, var=m.var, cov=m.cov)
+
+
+class SwAVTrainer(_TwoViewTrainer):
+    """SwAV pre-training (CONTRAST.MEM_TYPE 'swav'; CONTRAST.SWAV_K prototypes, Sinkhorn SWAV_EPS / SWAV_ITERS, temperature
+    SWAV_T): SimSiamTrainer's step with lib.modeling.graph_wrappers.SwAV as the model.  `out` carries `loss` and its two swapped
+    terms `l12`, `l21` (device scalars).  One GPU only: the Sinkhorn sums over the global batch need all-reduces between the
+    ranks inside every iteration."""
+
+    def _check_cfg(self, cfg):
+        if cfg.CONTRAST.MEM_TYPE != 'swav':
+            raise ValueError('SwAVTrainer needs CONTRAST.MEM_TYPE == swav (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if self.ctx.active:
+            raise NotImplementedError('SwAVTrainer runs on one GPU: the Sinkhorn sums over the global batch need all-reduces '
+                                      'between the ranks inside every iteration')
+
+    def _outputs(self, lv):
+        m = self.model.model
+        return dict(loss=lv.t, l12=m.l12, l21=m.l21)
 
 
 class ActionTrainer(_TrainerBase):

@@ -87,7 +87,8 @@ def get_defaults():
         'CHECKPOINT': dict(RESUME='none', CHECKNAME='video_model', CHECKPOINT_INTERVAL=20, NO_VAL=False,
                            FINETUNE=False, PRINT_FREQ=20),
         'CONTRAST': dict(MEM_TYPE='bank', NCE_K=65536, NCE_T=0.07, NCE_M=0.5, ALPHA=0.999, JIGSAW=False,
-                         BT_LAMBDA=0.0051, VIC_SIM=25.0, VIC_STD=25.0, VIC_COV=1.0),
+                         BT_LAMBDA=0.0051, VIC_SIM=25.0, VIC_STD=25.0, VIC_COV=1.0,
+                         SWAV_K=3000, SWAV_EPS=0.05, SWAV_T=0.1, SWAV_ITERS=3),
         'CROSS': dict(FEAT_DIM=128, HEAD_TYPE='mlp', MEM=None, BETA=0.5, MODALITY='visual',
                       CRITERION='crossentropy'),
     })

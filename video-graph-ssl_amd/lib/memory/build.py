@@ -1,11 +1,13 @@
 """Factories (reference: lib/memory/build.py).  Only what the pre-training configs select is on the
 HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no memory, the loss module itself) /
 'barlow' (Barlow Twins' cross-correlation loss, likewise the loss module itself) / 'vicreg' (the variance / invariance /
-covariance loss, likewise), CRITERION 'crossentropy'."""
+covariance loss, likewise) / 'swav' (the swapped-prediction loss, likewise; the prototypes live in the model), CRITERION
+'crossentropy'."""
 from .barlow import BarlowTwinsLoss
 from .criterion import NCESoftmaxLoss
 from .mem_moco import RGBMoCo
 from .ntxent import NTXent
+from .swav import SwAVLoss
 from .vicreg import VICRegLoss
 
 
@@ -22,6 +24,8 @@ def create_contrast(cfg, n_data):
         return BarlowTwinsLoss(cfg.CONTRAST.BT_LAMBDA)
     if cfg.CONTRAST.MEM_TYPE == 'vicreg':
         return VICRegLoss(cfg.CONTRAST.VIC_SIM, cfg.CONTRAST.VIC_STD, cfg.CONTRAST.VIC_COV)
+    if cfg.CONTRAST.MEM_TYPE == 'swav':
+        return SwAVLoss(cfg.CONTRAST.SWAV_EPS, cfg.CONTRAST.SWAV_T, cfg.CONTRAST.SWAV_ITERS)
     raise NotImplementedError('mem not suported: {}'.format(cfg.CONTRAST.MEM_TYPE))
 
 

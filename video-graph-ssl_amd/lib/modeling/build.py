@@ -21,13 +21,15 @@ def create_video_model(cfg):
 
 
 def create_visual_model(cfg):
-    """-> (model, model_ema | None); only MoCo has a key encoder ('simsiam', 'simclr', 'barlow' and 'vicreg' return None).  NOTE: the
+    """-> (model, model_ema | None); only MoCo has a key encoder (every other MEM_TYPE returns None).  NOTE: the
     reference never forwards MODEL.AUG_FLAG (dead code); here the flag is honoured so the graph block can actually be
     switched on."""
     model = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE,
                          nce_t=cfg.CONTRAST.NCE_T, bt_lambda=getattr(cfg.CONTRAST, 'BT_LAMBDA', 0.0051),
                          vic_coeffs=tuple(getattr(cfg.CONTRAST, k, d)
-                                          for k, d in (('VIC_SIM', 25.0), ('VIC_STD', 25.0), ('VIC_COV', 1.0))))
+                                          for k, d in (('VIC_SIM', 25.0), ('VIC_STD', 25.0), ('VIC_COV', 1.0))),
+                         swav_args=tuple(getattr(cfg.CONTRAST, k, d)
+                                         for k, d in (('SWAV_K', 3000), ('SWAV_EPS', 0.05), ('SWAV_T', 0.1), ('SWAV_ITERS', 3))))
     model_ema = None
     if cfg.CONTRAST.MEM_TYPE == 'moco':
         model_ema = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE)

@@ -1,5 +1,6 @@
-"""ContrastWrapper / SimSiam / GraphWrapper (reference: lib/modeling/graph_wrappers.py) on the engine, and SimCLR (the
-reference's ContrastWrapper trained with the in-batch NT-Xent loss; not in the reference).
+"""ContrastWrapper / SimSiam / GraphWrapper (reference: lib/modeling/graph_wrappers.py) on the engine, SimCLR (the
+reference's ContrastWrapper trained with the in-batch NT-Xent loss; not in the reference) and SwAV (the same wrapper with
+learned prototypes and the swapped-prediction loss; not in the reference either).
 
 ``GraphWrapper.forward(x)`` keeps the reference behaviour (MoCo: (b,3,T,H,W) -> (b,FEAT_DIM) unit
 rows; SimSiam and SimCLR: (b,6,T,H,W) -> scalar loss) and is differentiable through torch.autograd as ONE
@@ -204,9 +205,65 @@ class VICReg(nn.Module):
         return run_module(self, x).reshape(())
 
 
+class Prototypes(nn.Module):
+    """SwAV's K prototype vectors: a plain (K, dim) parameter with unit rows, drawn as nn.Linear's weight and normalised."""
+
+    def __init__(self, dim, K):
+        super().__init__()
+        w = nn.Linear(dim, K, bias=False).weight.detach()
+        self.weight = nn.Parameter(w / w.norm(dim=1, keepdim=True))
+
+
+class SwAV(ContrastWrapper):
+    """ContrastWrapper (encoder + projection head + Normalize) and K learned prototypes, trained with SwAV's swapped-prediction
+    loss on the two views of a (b,6,T,H,W) batch (state dict: ``encoder.*``, ``proj_head.*``, ``prototypes.weight``, so every
+    loader of MoCo / SimCLR checkpoints reads the encoder).  The views go through encoder + head in TWO passes, so BatchNorm
+    statistics are per view, as in this package's other two-view objectives.  No multi-crop, no feature queue and no frozen
+    prototypes (DESIGN.md)."""
+
+    def __init__(self, encoder, hid_dim=128, head_type='mlp', K=3000, eps=0.05, T=0.1, iters=3):
+        super().__init__(encoder, hid_dim, head_type)
+        self.eps, self.T, self.iters = ops.swav_params('SwAV', eps, T, iters)
+        if isinstance(K, bool) or int(K) != K or not 2 <= int(K) <= 65536:
+            raise ValueError('SwAV: the number of prototypes must lie in [2, 65536] (got %r)' % (K,))
+        self.prototypes = Prototypes(hid_dim, int(K))
+        self.l12 = self.l21 = None              # the two swapped terms of the last forward (device scalars)
+
+    def fwd(self, tape, xv):
+        """loss = (l12 + l21) / 2 of the two views' scores against the prototypes, both views through the encoder WITH grad.
+        A recording forward first renormalises the prototype rows in place, as the authors' training loop does before every
+        step."""
+        C = self.prototypes.weight
+        if tape.recording:
+            ops.rows_normalize_(C.data)
+        x = xv.t
+        x1, x2 = torch.chunk(x, 2, dim=1)          # views, read in place through the batch stride
+        z1 = ContrastWrapper.fwd(self, tape, Var(x1))
+        z2 = ContrastWrapper.fwd(self, tape, Var(x2))
+        a, b = z1.t.contiguous(), z2.t.contiguous()
+        parts, dS = ops.swav_fwd(a, b, C.data, self.eps, self.T, self.iters)
+        self.l12, self.l21 = parts[1:2], parts[2:3]
+        lv = Var(parts[:1], tape.recording)
+
+        def back():
+            # d loss / d (z1, z2, C) in two launches; the upstream scalar and the fp16-storage loss scale fold into their scale
+            g = lv.grad
+            gs = 1.0
+            if g is not None and g.numel() == 1 and not torch.cuda.is_current_stream_capturing():
+                gs = float(g.item())
+            dz1, dz2 = ops.swav_bwd(a, b, C.data, dS, L._grad_of(C), True, gscale_dev=ops.LOSS_SCALE_STATE[0], gscale_host=gs)
+            z1.add_grad(dz1)
+            z2.add_grad(dz2)
+        tape.record(back)
+        return lv
+
+    def forward(self, x):
+        return run_module(self, x).reshape(())
+
+
 class GraphWrapper(nn.Module):
     def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07, bt_lambda=0.0051,
-                 vic_coeffs=(25.0, 25.0, 1.0)):
+                 vic_coeffs=(25.0, 25.0, 1.0), swav_args=(3000, 0.05, 0.1, 3)):
         super().__init__()
         if mem_type == 'simsiam':
             self.model = SimSiam(encoder=encoder, hid_dim=hid_dim)
@@ -216,6 +273,8 @@ class GraphWrapper(nn.Module):
             self.model = BarlowTwins(encoder=encoder, hid_dim=hid_dim, lambd=bt_lambda)
         elif mem_type == 'vicreg':
             self.model = VICReg(encoder, hid_dim, *vic_coeffs)
+        elif mem_type == 'swav':
+            self.model = SwAV(encoder, hid_dim, head_type, *swav_args)
         else:
             self.model = ContrastWrapper(encoder=encoder, hid_dim=hid_dim, head_type=head_type)
 
