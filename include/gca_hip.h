@@ -649,6 +649,7 @@ int gca_vicreg_bwd(const float* z1, const float* z2, const float* stats, const f
  * GCA_EINVAL (nothing launched, nothing written; -1 from gca_swav_ws_bytes) for N outside [2, 8192], K outside [2, 65536],
  * D outside [1, 8192], iters outside [1, 16], eps outside [0.025, 1] (exp(-2 / eps) stays a normal fp32 number), T not
  * positive or T or 1 / T not finite in fp32, gscale_host not finite, any NULL pointer other than codes and gscale_dev.
+ * gca_swav_bwd never looks at how dS was made: it serves the DINO loss below as well (gca_dino_fwd's dS on the student's operands).
  * gca_rows_normalize: C[k,:] /= ||C[k,:]|| in place, one wave per row, an all-zero row left as it is; GCA_EINVAL for NULL,
  * K outside [1, 65536], D outside [1, 8192]. */
 int gca_rows_normalize(float* C, int64_t K, int64_t D, void* stream);
@@ -659,6 +660,42 @@ int gca_swav_dz_splits(int64_t N, int64_t D, int64_t K);
 int gca_swav_bwd(const float* z1, const float* z2, const float* C, const float* dS, int64_t N, int64_t D, int64_t K,
                  const float* gscale_dev, float gscale_host, float* dz1, float* dz2, float* dC, int accumulate_dC, void* ws,
                  void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * DINO: self-distillation from a centred momentum teacher (csrc/dino.hip; Caron et al. 2021).  Not in the reference.  Student
+ * features zs1, zs2 (N, D) and prototypes Cs (K, D), teacher features zt1, zt2 (N, D) and prototypes Ct (K, D), fp32 contiguous,
+ * all with unit rows (a precondition, not checked on the device); the centre `center` (K).  Per view v:
+ *   Ss_v = zs_v Cs^T     St_v = zt_v Ct^T  (N, K)     p_v = softmax((St_v - c) / Tt)  (rows; no gradient)
+ *   ls_v = Ss_v / Ts - lse(Ss_v / Ts)      l12 = -(1/N) sum_{n,k} p_1 ls_2      l21 = -(1/N) sum_{n,k} p_2 ls_1
+ *   loss = (l12 + l21) / 2                 ent = -(1/(2N)) sum_{v,n,k} p_v ((St_v - c) / Tt - lse_t)   (mean teacher entropy)
+ *   dSs_2 = (exp(ls_2) - p_1) / (2 N Ts)   dSs_1 = (exp(ls_1) - p_2) / (2 N Ts)
+ *   c' = cm c + (1 - cm) (1/(2N)) sum_{v,n} St_v[n,:]     written after the loss has used c, and only when update_center != 0
+ * parts[4] = loss, l12, l21, ent.  Ts and cm are host floats; the teacher temperature Tt is read from the one device float
+ * tt_dev, so a captured graph follows its warm-up schedule (the host that writes it checks it: positive, Tt and 1 / Tt finite).
+ * Saved state, caller-owned: dS (2, N, K), 8 N K bytes -- it holds the student scores until the row launch replaces them in
+ * place -- and is all the backward needs: gca_swav_bwd(zs1, zs2, Cs, dS, ...) gives dzs1, dzs2 and dCs.  probs: NULL, or
+ * (2, N, K) that receives p_1, p_2 (tests and monitoring).  `ws`: gca_dino_ws_bytes(N, D, K) = (2 N K + 4 N) 4 bytes: the teacher
+ * scores and the row terms; nothing in it outlives the call.
+ * Launches: 3 or 4.  The four products in one grid on v_mfma_f32_32x32x2_f32 (exact fp32), 64 x 64 tiles, all edges guarded;
+ * one 256-thread workgroup per row and direction (online max / sum of the teacher row and the student row, then a second
+ * sweep: probabilities, dS, the row's loss and entropy terms); the centre (column sums over the 2 N teacher rows, view 1
+ * first, then the EMA) behind it in stream order; the fp64 fold of the 2 N row terms.  No atomics: outputs are bitwise the
+ * same from call to call.  No host sync, allocation or read: capturable in a hipGraph.  One dispatch path, 4-byte accesses only.
+ * tests/dino_ref.py restates the arithmetic.
+ * GCA_EINVAL (nothing launched, nothing written; -1 from gca_dino_ws_bytes) for N outside [2, 8192], K outside [2, 65536],
+ * D outside [1, 8192], Ts not positive or Ts or 1 / Ts not finite in fp32, cm outside [0, 1), any NULL pointer other than
+ * probs. */
+enum { GCA_DINO_ROW_WORKGROUP = 0, GCA_DINO_ROW_WAVE = 1 };
+int64_t gca_dino_ws_bytes(int64_t N, int64_t D, int64_t K);
+int gca_dino_fwd(const float* zs1, const float* zs2, const float* Cs, const float* zt1, const float* zt2, const float* Ct, int64_t N,
+                 int64_t D, int64_t K, float Ts, const float* tt_dev, float cm, float* center, int update_center, float* parts,
+                 float* dS, float* probs, void* ws, void* stream);
+/* gca_dino_fwd with the row launch's grid chosen by the caller: GCA_DINO_ROW_WORKGROUP, what gca_dino_fwd uses, or
+ * GCA_DINO_ROW_WAVE, one wave per row and direction as SwAV's row kernels have it (tools/dino_micro.py times both; each is
+ * reproducible on its own, the two differ in their fold order).  GCA_EINVAL for any other row_grid. */
+int gca_dino_fwd_grid(const float* zs1, const float* zs2, const float* Cs, const float* zt1, const float* zt2, const float* Ct,
+                      int64_t N, int64_t D, int64_t K, float Ts, const float* tt_dev, float cm, float* center, int update_center,
+                      float* parts, float* dS, float* probs, int row_grid, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
@@ -696,6 +733,9 @@ int gca_classifier_bwd(const float* x, const float* w, const float* logits, cons
  * configured by make_optimizer (lib/solver/build.py:24-59: one group per parameter).
  * ------------------------------------------------------------------------------------- */
 int gca_ema_update(float* p_ema, const float* p, int64_t n, float m, void* stream);
+/* The same update with the momentum read from one device float (a captured step follows a momentum schedule); any n >= 1,
+ * no alignment required. */
+int gca_ema_update_dev(float* p_ema, const float* p, int64_t n, const float* m_dev, void* stream);
 /* seg table: per 256-element chunk i: lr[i], wd[i] (device arrays of length n/256).
  * grad_clip: NULL, or the 4-float result of gca_grad_clip_coef / gca_grad_unscale_clip -- every gradient is multiplied by
  * grad_clip[1] on the fly (the grads.mul_(clip_coef) pass of clip_grad_norm_ without a pass over the arena), and when

@@ -21,4 +21,5 @@ bash tools/pmc_conv.sh L00,L01,L02 wgrad > $E/sq_counters_wgrad.txt 2>&1 || echo
 rm -rf gpurun_out/pmc_conv
 timeout -k 10 600 python tools/vicreg_micro.py --out $E/vicreg_micro.json > $E/vicreg_micro.log 2>&1 || { echo vicreg_micro failed; tail -5 $E/vicreg_micro.log; }
 timeout -k 10 600 python tools/swav_micro.py --out $E/swav_micro.json > $E/swav_micro.log 2>&1 || { echo swav_micro failed; tail -5 $E/swav_micro.log; }
+timeout -k 10 600 python tools/dino_micro.py --out $E/dino_micro.json > $E/dino_micro.log 2>&1 || { echo dino_micro failed; tail -5 $E/dino_micro.log; }
 ls -la $E

@@ -106,6 +106,7 @@ SIGNATURES = {
     'gca_graph_gcn_bwd_ws_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     'gca_graph_gcn_bwd': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     'gca_ema_update': (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp]),
+    'gca_ema_update_dev': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     'gca_sgd_step': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_f32, c_i32, c_i32, c_vp, c_vp]),
     'gca_lars_job_chunks': (c_i32, []),
     'gca_lars_step': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32,
@@ -155,6 +156,11 @@ SIGNATURES = {
     'gca_swav_fwd': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'gca_swav_dz_splits': (c_i32, [c_i64, c_i64, c_i64]),
     'gca_swav_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'gca_dino_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
+    'gca_dino_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp,
+                             c_vp, c_vp]),
+    'gca_dino_fwd_grid': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp,
+                                  c_vp, c_i32, c_vp, c_vp]),
     'gca_classifier_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_classifier_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'gca_classifier_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32,

@@ -97,6 +97,25 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ pe, const 
   }
 }
 
+// One element of ema_kernel as the compiler contracts it there: (1 - m) b rounded, then one fused a m + that.  Spelled out so that
+// the element-wise tail below keeps ema_kernel's bits.
+__device__ __forceinline__ float ema_one(float a, float b, float m, float om) { return __fmaf_rn(a, m, __fmul_rn(om, b)); }
+
+// gca_ema_update with the momentum read from one device float (a captured step follows the momentum schedule).  Whole float4s
+// when both pointers are 16-byte aligned (n4 of them, else none), the remaining elements one by one.
+__global__ __launch_bounds__(256) void ema_dev_kernel(float* __restrict__ pe, const float* __restrict__ p, long long n4, long long n,
+                                                      const float* __restrict__ m_dev) {
+  const float m = *m_dev, om = 1.f - m;
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  for (long long i = gid; i < n4; i += stride) {
+    float4 a = reinterpret_cast<float4*>(pe)[i];
+    const float4 b = reinterpret_cast<const float4*>(p)[i];
+    a.x = ema_one(a.x, b.x, m, om); a.y = ema_one(a.y, b.y, m, om); a.z = ema_one(a.z, b.z, m, om); a.w = ema_one(a.w, b.w, m, om);
+    reinterpret_cast<float4*>(pe)[i] = a;
+  }
+  for (long long i = 4 * n4 + gid; i < n; i += stride) pe[i] = ema_one(pe[i], p[i], m, om);
+}
+
 // The LARS factor times d, rounded on its own (the pragma withholds the product from contraction): fused into
 // mom * buf + q * d it would round mom * buf instead, and a tensor with q == 1 would leave the SGD kernel's bits.
 __device__ __forceinline__ float lars_scaled(float q, float d) {
@@ -409,6 +428,14 @@ int gca_negcos_fwd_bwd(const float* p, const float* z, int64_t rows, int64_t dim
 int gca_ema_update(float* p_ema, const float* p, int64_t n, float m, void* stream) {
   if (!p_ema || !p || n <= 0 || (n & 3)) return GCA_EINVAL;
   hipLaunchKernelGGL(ema_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p_ema, p, (long long)(n / 4), m);
+  return gca_launch_status();
+}
+int gca_ema_update_dev(float* p_ema, const float* p, int64_t n, const float* m_dev, void* stream) {
+  if (!p_ema || !p || !m_dev || n <= 0) return GCA_EINVAL;
+  const bool aligned = (((uintptr_t)p_ema | (uintptr_t)p) & 15) == 0;
+  const long long n4 = aligned ? n / 4 : 0, rest = n - 4 * n4;
+  hipLaunchKernelGGL(ema_dev_kernel, dim3(ew_blocks(n4 > rest ? n4 : rest)), dim3(256), 0, (hipStream_t)stream, p_ema, p, n4,
+                     (long long)n, m_dev);
   return gca_launch_status();
 }
 int gca_sgd_step(float* p, const float* grad, float* mom_buf, int64_t n, const float* chunk_lr,

@@ -1133,6 +1133,85 @@ def swav_bwd(z1, z2, C, dS, dC, accumulate, gscale_dev=None, gscale_host=1.0):
     return dz1, dz2
 
 
+# ----------------------------------------------------------------------------- DINO
+def dino_temperature(what, T, name='Tt'):
+    """-> T as the kernels accept a temperature: positive, T and 1 / T finite in fp32; ValueError otherwise."""
+    T = float(T)
+    if not 1.2e-38 < T < 3.0e38:
+        raise ValueError('%s: %s must be positive, %s and 1 / %s finite in fp32 (got %r)' % (what, name, name, name, T))
+    return T
+
+
+def dino_params(what, Ts, Tt, cm):
+    """-> (Ts, Tt, cm) as gca_dino_fwd accepts them; ValueError otherwise (both temperatures positive with T and 1 / T finite
+    in fp32, the centre momentum cm in [0, 1))."""
+    import ctypes
+    Ts, Tt, cm = dino_temperature(what, Ts, 'Ts'), dino_temperature(what, Tt, 'Tt'), float(cm)
+    if not 0.0 <= ctypes.c_float(cm).value < 1.0:
+        raise ValueError('%s: cm must lie in [0, 1) (got %r)' % (what, cm))
+    return Ts, Tt, cm
+
+
+def _dino_args(zs1, zs2, Cs, zt1, zt2, Ct, center, what):
+    """Host-side refusals of gca_dino_fwd on the shapes (before any device is touched) -> (N, D, K)."""
+    N, D, K = _swav_args(zs1, zs2, Cs, what)
+    if _swav_args(zt1, zt2, Ct, what) != (N, D, K):
+        raise ValueError('%s: the teacher operands must have the student shapes (%d, %d), (%d, %d) (got %s, %s)'
+                         % (what, N, D, K, D, tuple(zt1.shape), tuple(Ct.shape)))
+    if center.dtype is not F32 or tuple(center.shape) != (K,) or not center.is_contiguous():
+        raise ValueError('%s: the centre is a contiguous (%d,) fp32 vector (got %s %s)' % (what, K, tuple(center.shape), center.dtype))
+    return N, D, K
+
+
+def dino_fwd(zs1, zs2, Cs, zt1, zt2, Ct, Ts, tt_dev, cm, center, update_center, want_probs=False, row_grid=None):
+    """DINO forward (gca_dino_fwd; tests/dino_ref.py states the arithmetic): the (N, D) fp32 unit-row features of the two views
+    from the student and from the teacher, the (K, D) unit-row prototypes of each, the student temperature Ts and centre
+    momentum cm (host floats), the teacher temperature tt_dev (ONE fp32 on the device, checked by whoever writes it) and the
+    (K,) centre, which is updated in place after the loss has used it when `update_center` -> (parts = [loss, l12, l21, ent],
+    dS (2, N, K)[, probs (2, N, K)]), all on the device.  dS, 8 N K bytes, is d loss / d (Ss_1, Ss_2) and all that dino_bwd
+    needs.  row_grid: None, or 0 / 1 for gca_dino_fwd_grid's workgroup / wave per row (the micro-benchmark's switch).
+    ValueError for arguments the kernel entry refuses."""
+    if row_grid not in (None, 0, 1):
+        raise ValueError('dino_fwd: row_grid is None, 0 (workgroup per row) or 1 (wave per row) (got %r)' % (row_grid,))
+    N, D, K = _dino_args(zs1, zs2, Cs, zt1, zt2, Ct, center, 'dino_fwd')
+    Ts, _, cm = dino_params('dino_fwd', Ts, 1.0, cm)
+    if tt_dev.dtype is not F32 or tt_dev.numel() != 1:
+        raise ValueError('dino_fwd: tt_dev is one fp32 on the device (got %s %s)' % (tuple(tt_dev.shape), tt_dev.dtype))
+    zs1, zs2, Cs, zt1, zt2, Ct = (t.contiguous() for t in (zs1, zs2, Cs, zt1, zt2, Ct))
+    ps = [ptr(t) for t in (zs1, zs2, Cs, zt1, zt2, Ct)]                 # (RuntimeError for host tensors)
+    dev = zs1.device
+    parts = torch.empty(4, dtype=F32, device=dev)
+    dS = torch.empty((2, N, K), dtype=F32, device=dev)
+    probs = torch.empty((2, N, K), dtype=F32, device=dev) if want_probs else None
+    ws = WS.get(H.lib.gca_dino_ws_bytes(N, D, K), dev)
+    tail = (ptr(ws), stream())
+    H.call('gca_dino_fwd' if row_grid is None else 'gca_dino_fwd_grid', *ps, N, D, K, Ts, ptr(tt_dev), cm, ptr(center),
+           int(bool(update_center)), ptr(parts), ptr(dS), ptr(probs), *(tail if row_grid is None else (int(row_grid),) + tail))
+    return (parts, dS, probs) if want_probs else (parts, dS)
+
+
+def dino_bwd(zs1, zs2, Cs, dS, dC, accumulate, gscale_dev=None, gscale_host=1.0):
+    """d loss / d (zs1, zs2) of dino_fwd from its saved dS, times gscale_host * (*gscale_dev if given) -> (dz1, dz2); the student
+    prototypes' gradient, scaled alike, goes into dC (K, D) (added to it with `accumulate`).  The products are SwAV's:
+    gca_swav_bwd never looks at how dS was made."""
+    N, D, K = _swav_args(zs1, zs2, Cs, 'dino_bwd')
+    gscale_host = float(gscale_host)
+    if not -3.0e38 < gscale_host < 3.0e38:
+        raise ValueError('dino_bwd: gscale_host must be finite in fp32 (got %r)' % gscale_host)
+    if dS.dtype is not F32 or tuple(dS.shape) != (2, N, K):
+        raise ValueError('dino_bwd: dS is the (2, %d, %d) fp32 tensor of dino_fwd (got %s %s)' % (N, K, tuple(dS.shape), dS.dtype))
+    if dC.dtype is not F32 or tuple(dC.shape) != (K, D) or not dC.is_contiguous():
+        raise ValueError('dino_bwd: dC is a contiguous (%d, %d) fp32 matrix (got %s %s)' % (K, D, tuple(dC.shape), dC.dtype))
+    zs1, zs2, Cs, dS = (t.contiguous() for t in (zs1, zs2, Cs, dS))
+    p1, p2, pc = ptr(zs1), ptr(zs2), ptr(Cs)
+    dz1 = torch.empty((N, D), dtype=F32, device=zs1.device)
+    dz2 = torch.empty((N, D), dtype=F32, device=zs1.device)
+    ws = WS.get(H.lib.gca_swav_ws_bytes(N, D, K), zs1.device)
+    H.call('gca_swav_bwd', p1, p2, pc, ptr(dS), N, D, K, ptr(gscale_dev), gscale_host, ptr(dz1), ptr(dz2), ptr(dC),
+           int(bool(accumulate)), ptr(ws), stream())
+    return dz1, dz2
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
@@ -1248,6 +1327,19 @@ def graph_gcn_bwd(adj, s, dout, want_dadj=True):
 # ----------------------------------------------------------------------------- flat-arena updates
 def ema_update(p_ema, p, m):
     H.call('gca_ema_update', ptr(p_ema), ptr(p), p.numel(), float(m), stream())
+
+
+def ema_update_dev(p_ema, p, m_dev):
+    """ema_update with the momentum read from `m_dev`, ONE fp32 on the device (gca_ema_update_dev): a captured step follows
+    a momentum schedule.  p_ema and p are contiguous fp32 of one size, any length >= 1."""
+    if p_ema.dtype is not F32 or p.dtype is not F32 or p_ema.numel() != p.numel() or p.numel() < 1:
+        raise ValueError('ema_update_dev: p_ema and p are fp32 tensors of one size >= 1 (got %s %s, %s %s)'
+                         % (tuple(p_ema.shape), p_ema.dtype, tuple(p.shape), p.dtype))
+    if not (p_ema.is_contiguous() and p.is_contiguous()):
+        raise ValueError('ema_update_dev: p_ema and p must be contiguous')
+    if m_dev.dtype is not F32 or m_dev.numel() != 1:
+        raise ValueError('ema_update_dev: m_dev is one fp32 on the device (got %s %s)' % (tuple(m_dev.shape), m_dev.dtype))
+    H.call('gca_ema_update_dev', ptr(p_ema), ptr(p), p.numel(), ptr(m_dev), stream())
 
 
 def sgd_step(p, g, buf, chunk_lr, chunk_wd, lr_scale, momentum, nesterov, grad_clip=None):

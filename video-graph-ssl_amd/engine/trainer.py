@@ -1,4 +1,4 @@
-"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins, VICReg and SwAV) on the HIP engine.
+"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins, VICReg, SwAV and DINO) on the HIP engine.
 
 Restates the iteration of tools/train_video_contrast_dis.py:395-454 (_train_moco) and :479-523
 (_train_simsiam) without its host syncs (3x .item() per iteration, :429-431) and defects
@@ -497,13 +497,17 @@ class _TwoViewTrainer(_TrainerBase):
     def _outputs(self, lv):
         return dict(loss=lv.t)
 
+    def _loss(self, tape):
+        """The loss Var of the static batch, its backward recorded on `tape`."""
+        return self.model.fwd(tape, Var(self._static))
+
     def _fwd_bwd(self, upto=0):
         """Forward, loss and the backward pass down to tape index `upto` (0 = all of it; N > 1 runs the rest in stages)."""
         self.optimizer.zero_grad()
         if self._packer is not None:
             self._packer.run()
         tape = Tape(True)
-        lv = self.model.fwd(tape, Var(self._static))
+        lv = self._loss(tape)
         self.out = self._outputs(lv)
         ops.LOSS_SCALE_STATE[0] = self.scale_state            # fp16 storage: the model's loss-gradient seed is scaled by S
         try:
@@ -690,6 +694,124 @@ class SwAVTrainer(_TwoViewTrainer):
     def _outputs(self, lv):
         m = self.model.model
         return dict(loss=lv.t, l12=m.l12, l21=m.l21)
+
+
+class DINOTrainer(_TwoViewTrainer):
+    """DINO pre-training (CONTRAST.MEM_TYPE 'dino'; CONTRAST.DINO_K prototypes, student / teacher temperatures DINO_TS / DINO_TT,
+    centre momentum DINO_CM, teacher momentum CONTRAST.ALPHA): self-distillation from a momentum teacher.  The student is
+    _TwoViewTrainer's model (lib.modeling.graph_wrappers.DINO: both views through it with gradients); the teacher is a second
+    wrapper of the same layout that sees both views without a tape (BatchNorm in train mode, as MoCo's key encoder) and follows
+    the student as an EMA over the whole parameter arena, prototypes included.  One step:
+
+        teacher forward, both views (no tape)            student forward, both views (tape)
+        both prototype matrices renormalised             dino_fwd: loss, dS, centre update       dino_bwd -> tape backward
+        optimizer step                                   EMA of the teacher (momentum read from the device)
+
+    The teacher temperature and the teacher momentum live in one device float each, read by the kernels, so the captured
+    step follows their schedules (lib.solver.dino_teacher_temp / cosine_momentum) through set_schedule without re-capture.
+    `out` carries `loss`, `l12`, `l21` and `ent` (the mean teacher entropy: log K or 0 when collapsed) as device scalars.
+    One GPU only: the centre's column mean over the global batch needs an all-reduce between the ranks."""
+
+    def __init__(self, cfg, device, ctx=None, use_graph=True, seed=None):
+        super().__init__(cfg, device, ctx, use_graph, seed)
+        self.model_ema.to(self.device)
+        self.arena_t = arena_of(self.model_ema)
+        if self.arena_t.total != self.arena.total:
+            raise RuntimeError('student and teacher must share one parameter layout')
+        self.arena_t.flat.copy_(self.arena.flat)                          # the teacher starts as the student
+        set_key_encoder_mode(self.model_ema)
+        self.contrast = create_contrast(cfg, 0).to(self.device)
+        self.teacher_temp, self.momentum = self.contrast.Tt, float(cfg.CONTRAST.ALPHA)
+        self.tt_dev = self.contrast.tt_dev(self.device)
+        self.m_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.set_schedule(self.teacher_temp, self.momentum)
+        self._packer_t, self._packer_t_of = None, None                     # the teacher's BatchedPacker, and the student's it was built next to
+
+    def _check_cfg(self, cfg):
+        if cfg.CONTRAST.MEM_TYPE != 'dino':
+            raise ValueError('DINOTrainer needs CONTRAST.MEM_TYPE == dino (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if self.ctx.active:
+            raise NotImplementedError("DINOTrainer runs on one GPU: the centre's column mean over the global batch needs an "
+                                      'all-reduce between the ranks')
+
+    def _check_model(self, ema):
+        if ema is None:
+            raise ValueError('DINOTrainer needs the EMA twin that create_visual_model returns for CONTRAST.MEM_TYPE == dino')
+        self.model_ema = ema                                              # the teacher; set up once the base class is done
+
+    def set_schedule(self, teacher_temp=None, momentum=None):
+        """Write the teacher temperature and / or the teacher momentum of the following steps into their device scalars
+        (outside the captured graph, which reads them).  ValueError for a temperature that is not positive with T and 1 / T
+        finite in fp32, or a momentum outside [0, 1]."""
+        if teacher_temp is not None:
+            teacher_temp = ops.dino_temperature('DINOTrainer.set_schedule', teacher_temp, 'teacher_temp')
+        if momentum is not None:
+            momentum = float(momentum)
+            if not 0.0 <= momentum <= 1.0:
+                raise ValueError('DINOTrainer.set_schedule: momentum must lie in [0, 1] (got %r)' % momentum)
+        if teacher_temp is not None:
+            self.teacher_temp = teacher_temp
+            self.contrast.set_teacher_temp(teacher_temp)
+        if momentum is not None:
+            self.momentum = momentum
+            self.m_dev.fill_(momentum)
+
+    def _loss(self, tape):
+        s, t, c = self.model.model, self.model_ema.model, self.contrast
+        x1, x2 = torch.chunk(self._static, 2, dim=1)               # views, read in place through the batch stride
+        packed = self._packer_t is not None and self._packer_t_of is self._packer
+        if packed:
+            self._packer_t.run()
+        zt1 = t.fwd(Tape(False), Var(x1)).t.contiguous()
+        zt2 = t.fwd(Tape(False), Var(x2)).t.contiguous()
+        if packed:
+            self._packer_t.release()
+        z1 = s.fwd(tape, Var(x1))
+        z2 = s.fwd(tape, Var(x2))
+        Cs, Ct = s.prototypes.weight, t.prototypes.weight
+        ops.rows_normalize_(Cs.data)
+        ops.rows_normalize_(Ct.data)
+        a, b = z1.t.contiguous(), z2.t.contiguous()
+        parts, dS = ops.dino_fwd(a, b, Cs.data, zt1, zt2, Ct.data, c.Ts, self.tt_dev, c.cm, c.center, True)
+        c.l12, c.l21, c.ent = parts[1:2], parts[2:3], parts[3:4]
+        lv = Var(parts[:1], True)
+
+        def back():
+            # d loss / d (zs1, zs2, Cs); the fp16-storage loss scale folds into the products' scale
+            dz1, dz2 = ops.dino_bwd(a, b, Cs.data, dS, L._grad_of(Cs), True, gscale_dev=ops.LOSS_SCALE_STATE[0])
+            z1.add_grad(dz1)
+            z2.add_grad(dz2)
+        tape.record(back)
+        return lv
+
+    def _outputs(self, lv):
+        c = self.contrast
+        return dict(loss=lv.t, l12=c.l12, l21=c.l21, ent=c.ent)
+
+    def _update(self):
+        super()._update()
+        ops.ema_update_dev(self.arena_t.flat, self.arena.flat, self.m_dev)
+
+    def train_step(self, images):
+        out = super().train_step(images)
+        if self._packer_t_of is not self._packer:                        # (re)built with the student's, after an eager step
+            self._packer_t, self._packer_t_of = BatchedPacker(self.model_ema, (0,)), self._packer
+        return out
+
+    def state_dict(self, epoch=0):
+        """_TwoViewTrainer's checkpoint plus the teacher (`model_ema`), the centre (`contrast`, in MoCo's place) and the two
+        schedule values."""
+        sd = super().state_dict(epoch)
+        sd.update(model_ema=self.model_ema.state_dict(), contrast=self.contrast.state_dict(), teacher_temp=self.teacher_temp,
+                  momentum=self.momentum)
+        return sd
+
+    def load_state_dict(self, sd):
+        epoch = super().load_state_dict(sd)
+        self.model_ema.load_state_dict(sd['model_ema'])
+        self.contrast.load_state_dict(sd['contrast'])
+        self.set_schedule(sd.get('teacher_temp'), sd.get('momentum'))
+        return epoch
 
 
 class ActionTrainer(_TrainerBase):

@@ -1,10 +1,11 @@
 """Factories (reference: lib/memory/build.py).  Only what the pre-training configs select is on the
 HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no memory, the loss module itself) /
 'barlow' (Barlow Twins' cross-correlation loss, likewise the loss module itself) / 'vicreg' (the variance / invariance /
-covariance loss, likewise) / 'swav' (the swapped-prediction loss, likewise; the prototypes live in the model), CRITERION
-'crossentropy'."""
+covariance loss, likewise) / 'swav' (the swapped-prediction loss, likewise; the prototypes live in the model) / 'dino' (the centred-teacher
+self-distillation loss; its centre is the module's one buffer), CRITERION 'crossentropy'."""
 from .barlow import BarlowTwinsLoss
 from .criterion import NCESoftmaxLoss
+from .dino import DINOLoss
 from .mem_moco import RGBMoCo
 from .ntxent import NTXent
 from .swav import SwAVLoss
@@ -26,6 +27,8 @@ def create_contrast(cfg, n_data):
         return VICRegLoss(cfg.CONTRAST.VIC_SIM, cfg.CONTRAST.VIC_STD, cfg.CONTRAST.VIC_COV)
     if cfg.CONTRAST.MEM_TYPE == 'swav':
         return SwAVLoss(cfg.CONTRAST.SWAV_EPS, cfg.CONTRAST.SWAV_T, cfg.CONTRAST.SWAV_ITERS)
+    if cfg.CONTRAST.MEM_TYPE == 'dino':
+        return DINOLoss(cfg.CONTRAST.DINO_K, cfg.CONTRAST.DINO_TS, cfg.CONTRAST.DINO_TT, cfg.CONTRAST.DINO_CM)
     raise NotImplementedError('mem not suported: {}'.format(cfg.CONTRAST.MEM_TYPE))
 
 

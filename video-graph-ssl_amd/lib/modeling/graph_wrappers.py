@@ -1,6 +1,7 @@
 """ContrastWrapper / SimSiam / GraphWrapper (reference: lib/modeling/graph_wrappers.py) on the engine, SimCLR (the
 reference's ContrastWrapper trained with the in-batch NT-Xent loss; not in the reference) and SwAV (the same wrapper with
-learned prototypes and the swapped-prediction loss; not in the reference either).
+learned prototypes and the swapped-prediction loss; not in the reference either) and DINO (the same wrapper with prototypes,
+built twice -- student and momentum teacher -- and trained by DINOTrainer; not in the reference either).
 
 ``GraphWrapper.forward(x)`` keeps the reference behaviour (MoCo: (b,3,T,H,W) -> (b,FEAT_DIM) unit
 rows; SimSiam and SimCLR: (b,6,T,H,W) -> scalar loss) and is differentiable through torch.autograd as ONE
@@ -261,9 +262,24 @@ class SwAV(ContrastWrapper):
         return run_module(self, x).reshape(())
 
 
+class DINO(ContrastWrapper):
+    """ContrastWrapper (encoder + projection head + Normalize) and K prototypes: the student, and in a second instance of the
+    same layout the momentum teacher, of DINO's self-distillation (state dict: ``encoder.*``, ``proj_head.*``,
+    ``prototypes.weight``, so every loader of MoCo / SimCLR checkpoints reads the encoder).  ``forward(x)`` / ``fwd`` are
+    ContrastWrapper's: (b,3,T,H,W) -> (b, hid_dim) unit rows; the loss (lib.memory.dino.DINOLoss, csrc/dino.hip) needs both
+    instances and lives in the trainer.  The paper's GELU / bottleneck head and the weight-normalised last layer are not built:
+    the existing ProjectHead + Normalize feeds unit-row prototypes that the trainer renormalises before every step."""
+
+    def __init__(self, encoder, hid_dim=128, head_type='mlp', K=4096):
+        super().__init__(encoder, hid_dim, head_type)
+        if isinstance(K, bool) or int(K) != K or not 2 <= int(K) <= 65536:
+            raise ValueError('DINO: the number of prototypes must lie in [2, 65536] (got %r)' % (K,))
+        self.prototypes = Prototypes(hid_dim, int(K))
+
+
 class GraphWrapper(nn.Module):
     def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07, bt_lambda=0.0051,
-                 vic_coeffs=(25.0, 25.0, 1.0), swav_args=(3000, 0.05, 0.1, 3)):
+                 vic_coeffs=(25.0, 25.0, 1.0), swav_args=(3000, 0.05, 0.1, 3), dino_k=4096):
         super().__init__()
         if mem_type == 'simsiam':
             self.model = SimSiam(encoder=encoder, hid_dim=hid_dim)
@@ -275,6 +291,8 @@ class GraphWrapper(nn.Module):
             self.model = VICReg(encoder, hid_dim, *vic_coeffs)
         elif mem_type == 'swav':
             self.model = SwAV(encoder, hid_dim, head_type, *swav_args)
+        elif mem_type == 'dino':
+            self.model = DINO(encoder, hid_dim, head_type, dino_k)
         else:
             self.model = ContrastWrapper(encoder=encoder, hid_dim=hid_dim, head_type=head_type)
 

@@ -58,3 +58,27 @@ class WarmupMultiStepLR(object):
 
     def load_state_dict(self, sd):
         self.step(sd['last_epoch'])
+
+
+# ----------------------------------------------------------------------------- DINO's two host-side schedules
+def dino_teacher_temp(epoch, warmup_epochs, start, end):
+    """The teacher temperature of `epoch` (0-based): linear from `start` to `end` over the first `warmup_epochs` epochs, then
+    flat at `end` (Caron et al. 2021: 0.04 -> 0.07 over 30 epochs)."""
+    epoch, warmup_epochs, start, end = float(epoch), float(warmup_epochs), float(start), float(end)
+    if epoch < 0 or warmup_epochs < 0 or not (start > 0 and end > 0):
+        raise ValueError('dino_teacher_temp: epoch >= 0, warmup_epochs >= 0, positive temperatures (got %r, %r, %r, %r)'
+                         % (epoch, warmup_epochs, start, end))
+    if epoch >= warmup_epochs:
+        return end
+    return start + (end - start) * epoch / warmup_epochs
+
+
+def cosine_momentum(it, total, base):
+    """The teacher momentum of iteration `it` of `total`: a half cosine from `base` at it = 0 to 1 at it = total."""
+    import math
+    it, total, base = float(it), float(total), float(base)
+    if total <= 0 or not 0 <= it <= total or not 0.0 <= base <= 1.0:
+        raise ValueError('cosine_momentum: 0 <= it <= total, total > 0, 0 <= base <= 1 (got %r, %r, %r)' % (it, total, base))
+    if it == total:
+        return 1.0
+    return 1.0 - (1.0 - base) * 0.5 * (1.0 + math.cos(math.pi * it / total))
