@@ -698,6 +698,51 @@ int gca_dino_fwd_grid(const float* zs1, const float* zs2, const float* Cs, const
                       float* parts, float* dS, float* probs, int row_grid, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * MoCo v3: the queue-free, symmetrised cross-view InfoNCE of Chen, Xie, He 2021 (Algorithm 1) and its gradient
+ * (csrc/mocov3.hip).  Not in the reference.  q1, q2 (N, D) fp32 contiguous: the student's predictor outputs of the two views;
+ * k1, k2 (N, D): the momentum teacher's projector outputs (rows need not be unit-norm).  Direction 0 pairs (q, k) = (q1, k2),
+ * direction 1 pairs (q2, k1); per direction d:
+ *   s[i,j]  = (sum_e q[i,e] * k[j,e]) * inv_T
+ *   lse[i]  = m_i + log sum_j exp(s[i,j] - m_i),  m_i = max_j s[i,j]      (ALL j: the positive is inside the softmax)
+ *   sp[i]   = s[i,i]
+ *   l_d     = (1/N) sum_i (lse[i] - sp[i])
+ *   rank[i] = #{ j != i : s[i,j] >= sp[i] }                              (top-k hit iff rank < k)
+ *   P[i,j]  = exp(s[i,j] - lse[i])
+ *   dq[i,:] = g * w * inv_T / N * ( sum_j P[i,j] k[j,:] - k[i,:] ),   g = gscale_host * (gscale_dev ? *gscale_dev : 1)
+ *   loss    = w * (l_0 + l_1)          (the paper: w = 2 T).  Nothing flows to k1 / k2: the teacher is detached.
+ * row_lse, pos_logit, rank_ge hold 2 N entries, direction 0 first; loss holds 3 floats: w (l_0 + l_1), l_0, l_1.
+ * Guarantees:
+ *   products     v_mfma_f32_32x32x2_f32 (exact fp32, fp32 accumulation, bitwise an fmaf chain); no N x N tensor is formed.
+ *   one grid     both directions of a pass run in ONE grid.  Launches: forward 2 (tiles, then the fold of the column splits +
+ *                losses), backward 2 (tiles, then the fold of the column splits, the -k[i,:] term and the scale).
+ *   positive     sp[i] is the diagonal of the diagonal tile, computed first by the same k-ordered fma chain as the streamed
+ *                s[i,i]: ties with the positive compare equal.
+ *   forward      online max, sum and count per row; column splits folded in split order.
+ *   backward     a workgroup owns a 32-row tile of dq and streams the tiles of k; the s tile is recomputed transposed, so P is
+ *                already the A operand of sum_j P[i,j] k[j,:] (no trip through LDS); the fast path holds the whole dq tile in
+ *                accumulators; splits go to `ws` and are added in split order.  It recomputes s by the forward's chain:
+ *                N = 1 gives lse == sp, loss 0 and dq exactly 0.
+ *   determinism  no atomics, one owner per output element, fixed fold orders: outputs are bitwise the same from call to call.
+ *   capture      no host sync, allocation or read: both entries can be captured in a hipGraph.
+ *   dispatch     a function of the arguments alone, never of the device.  gca_mocov3_path reports it (`aligned`: every
+ *                pointer, outputs and ws included, 16-byte aligned): returns 1 for the fast path (D <= 256, D % 4 == 0,
+ *                aligned; 4 waves per workgroup, float4 loads with the next piece in flight under the current MFMAs, s
+ *                accumulated over 128-feature chunks -- two are what the LDS holds next to the four wave tiles), 0 for the
+ *                generic one (1 wave), and writes the waves per workgroup and the number of tile splits (ntxent's rule, per
+ *                direction) when the pointers are non-NULL.  tests/mocov3_ref.py restates arithmetic and dispatch.
+ * pos_logit and rank_ge may be NULL.  `ws`: gca_mocov3_ws_bytes(N, D) bytes (always > 0 for valid sizes), shared by both.
+ * GCA_EINVAL (nothing launched, nothing written; -1 from gca_mocov3_ws_bytes) for N < 1, N > 65536, D < 1, N * D >= 2^31,
+ * inv_T or w not finite or <= 0, a NULL q1 / q2 / k1 / k2 / row_lse / loss / dq1 / dq2 / ws, and in the backward entry dq1 or
+ * dq2 overlapping each other or any of q1, q2, k1, k2 (dq is written while other workgroups still read the inputs). */
+int64_t gca_mocov3_ws_bytes(int64_t N, int64_t D);
+int gca_mocov3_path(int64_t N, int64_t D, int aligned, int32_t* waves, int32_t* splits);
+int gca_mocov3_fwd(const float* q1, const float* q2, const float* k1, const float* k2, int64_t N, int64_t D, float inv_T,
+                   float w, float* row_lse, float* pos_logit, int32_t* rank_ge, float* loss, void* ws, void* stream);
+int gca_mocov3_bwd(const float* q1, const float* q2, const float* k1, const float* k2, const float* row_lse, int64_t N,
+                   int64_t D, float inv_T, float w, const float* gscale_dev, float gscale_host, float* dq1, float* dq2, void* ws,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

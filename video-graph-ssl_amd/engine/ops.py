@@ -1212,6 +1212,67 @@ def dino_bwd(zs1, zs2, Cs, dS, dC, accumulate, gscale_dev=None, gscale_host=1.0)
     return dz1, dz2
 
 
+# ----------------------------------------------------------------------------- MoCo v3
+def mocov3_weight(inv_T):
+    """The loss weight 2 T of Algorithm 1 as the host rounds it to fp32."""
+    return float(torch.tensor(2.0 / float(inv_T), dtype=F32).item())
+
+
+def _mocov3_args(q1, q2, k1, k2, inv_T, w, what):
+    """Host-side refusals of gca_mocov3_fwd / _bwd (before any device is touched) -> (N, D, inv_T, w)."""
+    for t in (q1, q2, k1, k2):
+        if t.dim() != 2 or t.dtype is not F32 or t.shape != q1.shape:
+            raise ValueError('%s: q1, q2, k1, k2 are (N, D) fp32 matrices of one shape (got %s)'
+                             % (what, ', '.join('%s %s' % (tuple(u.shape), u.dtype) for u in (q1, q2, k1, k2))))
+    N, D = q1.shape
+    if N < 1 or N > 65536 or D < 1 or N * D >= 2 ** 31:
+        raise ValueError('%s: 1 <= N <= 65536, D >= 1, N * D < 2^31 (got N=%d, D=%d)' % (what, N, D))
+    inv_T = float(inv_T)
+    if not 0.0 < inv_T < 3.0e38:
+        raise ValueError('%s: 1 / T must be positive and finite in fp32 (got %r)' % (what, inv_T))
+    w = mocov3_weight(inv_T) if w is None else float(w)
+    if not 0.0 < w < 3.0e38:
+        raise ValueError('%s: the loss weight must be positive and finite in fp32 (got %r)' % (what, w))
+    return N, D, inv_T, w
+
+
+def mocov3_fwd(q1, q2, k1, k2, inv_T, want_rank=False, w=None, want_pos=False):
+    """MoCo v3's symmetrised InfoNCE forward (gca_mocov3_fwd; tests/mocov3_ref.py states the arithmetic): the (N, D) fp32 student
+    rows q1, q2 and teacher rows k1, k2 of the two views -> (loss (3,): w (l_0 + l_1), l_0, l_1; lse (2 N,); rank (2, N) int32
+    or None; pos_logit (2 N,) or None), all on the device; direction 0 is q1 against k2, direction 1 q2 against k1.  rank[d, i]
+    counts the other columns that score at least row i's positive (top-k hit iff rank < k).  w defaults to 2 T rounded to fp32.
+    ValueError for arguments the kernel entry refuses."""
+    N, D, inv_T, w = _mocov3_args(q1, q2, k1, k2, inv_T, w, 'mocov3_fwd')
+    q1, q2, k1, k2 = (t.contiguous() for t in (q1, q2, k1, k2))
+    ps = [ptr(t) for t in (q1, q2, k1, k2)]                             # (RuntimeError for host tensors)
+    dev = q1.device
+    loss = torch.empty(3, dtype=F32, device=dev)
+    lse = torch.empty(2 * N, dtype=F32, device=dev)
+    rank = torch.empty((2, N), dtype=torch.int32, device=dev) if want_rank else None
+    pos = torch.empty(2 * N, dtype=F32, device=dev) if want_pos else None
+    ws = WS.get(H.lib.gca_mocov3_ws_bytes(N, D), dev)
+    H.call('gca_mocov3_fwd', *ps, N, D, inv_T, w, ptr(lse), ptr(pos), ptr(rank), ptr(loss), ptr(ws), stream())
+    return loss, lse, rank, pos
+
+
+def mocov3_bwd(q1, q2, k1, k2, lse, inv_T, gscale_dev=None, gscale_host=1.0, w=None):
+    """d loss / d (q1, q2) of mocov3_fwd from its row log-sum-exps, times gscale_host * (*gscale_dev if given) -> (dq1, dq2).
+    Nothing flows to k1, k2."""
+    N, D, inv_T, w = _mocov3_args(q1, q2, k1, k2, inv_T, w, 'mocov3_bwd')
+    gscale_host = float(gscale_host)
+    if not -3.0e38 < gscale_host < 3.0e38:
+        raise ValueError('mocov3_bwd: gscale_host must be finite in fp32 (got %r)' % gscale_host)
+    if lse.dtype is not F32 or tuple(lse.shape) != (2 * N,):
+        raise ValueError('mocov3_bwd: lse is the (2 N,) fp32 vector of mocov3_fwd (got %s %s)' % (tuple(lse.shape), lse.dtype))
+    q1, q2, k1, k2, lse = (t.contiguous() for t in (q1, q2, k1, k2, lse))
+    ps = [ptr(t) for t in (q1, q2, k1, k2, lse)]
+    dq1 = torch.empty((N, D), dtype=F32, device=q1.device)
+    dq2 = torch.empty((N, D), dtype=F32, device=q1.device)
+    ws = WS.get(H.lib.gca_mocov3_ws_bytes(N, D), q1.device)
+    H.call('gca_mocov3_bwd', *ps, N, D, inv_T, w, ptr(gscale_dev), gscale_host, ptr(dq1), ptr(dq2), ptr(ws), stream())
+    return dq1, dq2
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

@@ -1,4 +1,4 @@
-"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins, VICReg, SwAV and DINO) on the HIP engine.
+"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins, VICReg, SwAV, DINO and MoCo v3) on the HIP engine.
 
 Restates the iteration of tools/train_video_contrast_dis.py:395-454 (_train_moco) and :479-523
 (_train_simsiam) without its host syncs (3x .item() per iteration, :429-431) and defects
@@ -811,6 +811,125 @@ class DINOTrainer(_TwoViewTrainer):
         self.model_ema.load_state_dict(sd['model_ema'])
         self.contrast.load_state_dict(sd['contrast'])
         self.set_schedule(sd.get('teacher_temp'), sd.get('momentum'))
+        return epoch
+
+
+class MoCoV3Trainer(_TwoViewTrainer):
+    """MoCo v3 pre-training (CONTRAST.MEM_TYPE 'mocov3'; output width CROSS.FEAT_DIM, hidden width CONTRAST.V3_HID, temperature
+    CONTRAST.NCE_T, teacher momentum CONTRAST.ALPHA): Algorithm 1 of Chen, Xie, He 2021.  The student is _TwoViewTrainer's model
+    (lib.modeling.graph_wrappers.MoCoV3: encoder + projector + predictor, both views through it with gradients); the teacher is
+    a second wrapper without the predictor that sees both views without a tape (BatchNorm in train mode, as MoCo's key encoder)
+    and follows the student's encoder and projector as an EMA.  One step:
+
+        teacher forward, both views (no tape) -> k1, k2       student forward, both views (tape) -> q1, q2
+        mocov3_fwd: 2 T (CE(q1 k2^T / T) + CE(q2 k1^T / T))   mocov3_bwd -> tape backward
+        optimizer step                                        THEN the EMA of the teacher (keys came from the pre-update teacher)
+
+    The teacher's parameter arena is exactly the leading part of the student's (same names, same offsets, the predictor last;
+    checked at construction), so the EMA is ONE launch over arena.flat[:arena_t.total] with the momentum read from a device
+    float: the captured step follows lib.solver.cosine_momentum through set_schedule without re-capture.  BatchNorm buffers
+    are not averaged.  `out` carries `loss`, `l12`, `l21` (device scalars) and `rank` (2, N) int32.  The loss of a step is
+    _pair_loss alone: BYOL would be this trainer with gca_negcos_fwd_bwd there.  One GPU only: the keys of the global batch
+    need an all-gather between the ranks."""
+
+    def __init__(self, cfg, device, ctx=None, use_graph=True, seed=None):
+        super().__init__(cfg, device, ctx, use_graph, seed)
+        self.model_ema.to(self.device)
+        self.arena_t = arena_of(self.model_ema)
+        a, t = self.arena, self.arena_t
+        n = len(t.names)
+        if not (n < len(a.names) and a.names[:n] == t.names and a.offsets[:n] == t.offsets and a.sizes[:n] == t.sizes
+                and t.total == a.offsets[n] and all('.prediction.' in k for k in a.names[n:])
+                and not any('.prediction.' in k for k in t.names)):
+            raise RuntimeError("the teacher's parameter arena must be the leading part of the student's (same names and offsets, "
+                               'the predictor last)')
+        t.flat.copy_(a.flat[:t.total])                                     # the teacher starts as the student
+        set_key_encoder_mode(self.model_ema)
+        self.contrast = create_contrast(cfg, 0)
+        self.inv_T = 1.0 / self.contrast.T
+        self.momentum = float(cfg.CONTRAST.ALPHA)
+        self.m_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.set_schedule(self.momentum)
+        self._packer_t, self._packer_t_of = None, None                     # the teacher's BatchedPacker, and the student's it was built next to
+        self._l12 = self._l21 = self._rank = None
+
+    def _check_cfg(self, cfg):
+        if cfg.CONTRAST.MEM_TYPE != 'mocov3':
+            raise ValueError('MoCoV3Trainer needs CONTRAST.MEM_TYPE == mocov3 (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if self.ctx.active:
+            raise NotImplementedError('MoCoV3Trainer runs on one GPU: the keys of the global batch need an all-gather between '
+                                      'the ranks')
+
+    def _check_model(self, ema):
+        if ema is None:
+            raise ValueError('MoCoV3Trainer needs the EMA twin that create_visual_model returns for CONTRAST.MEM_TYPE == mocov3')
+        self.model_ema = ema                                              # the teacher; set up once the base class is done
+
+    def set_schedule(self, momentum=None):
+        """Write the teacher momentum of the following steps into its device scalar (outside the captured graph, which reads
+        it).  ValueError for a momentum outside [0, 1]."""
+        if momentum is not None:
+            momentum = float(momentum)
+            if not 0.0 <= momentum <= 1.0:
+                raise ValueError('MoCoV3Trainer.set_schedule: momentum must lie in [0, 1] (got %r)' % momentum)
+            self.momentum = momentum
+            self.m_dev.fill_(momentum)
+
+    def _pair_loss(self, q1, q2, k1, k2):
+        """The loss of the student rows q1, q2 against the teacher rows k1, k2 -> (loss (1,), backward() -> (dq1, dq2))."""
+        loss, lse, self._rank, _ = ops.mocov3_fwd(q1, q2, k1, k2, self.inv_T, want_rank=True)
+        self._l12, self._l21 = loss[1:2], loss[2:3]
+
+        def backward():
+            # the fp16-storage loss scale folds into the products' scale
+            return ops.mocov3_bwd(q1, q2, k1, k2, lse, self.inv_T, gscale_dev=ops.LOSS_SCALE_STATE[0])
+        return loss[:1], backward
+
+    def _loss(self, tape):
+        s, t = self.model.model, self.model_ema.model
+        x1, x2 = torch.chunk(self._static, 2, dim=1)               # views, read in place through the batch stride
+        packed = self._packer_t is not None and self._packer_t_of is self._packer
+        if packed:
+            self._packer_t.run()
+        k1 = t.fwd(Tape(False), Var(x1)).t.contiguous()
+        k2 = t.fwd(Tape(False), Var(x2)).t.contiguous()
+        if packed:
+            self._packer_t.release()
+        z1 = s.fwd(tape, Var(x1))
+        z2 = s.fwd(tape, Var(x2))
+        loss, backward = self._pair_loss(z1.t.contiguous(), z2.t.contiguous(), k1, k2)
+        lv = Var(loss, True)
+
+        def back():
+            dq1, dq2 = backward()
+            z1.add_grad(dq1)
+            z2.add_grad(dq2)
+        tape.record(back)
+        return lv
+
+    def _outputs(self, lv):
+        return dict(loss=lv.t, l12=self._l12, l21=self._l21, rank=self._rank)
+
+    def _update(self):
+        super()._update()
+        ops.ema_update_dev(self.arena_t.flat, self.arena.flat[:self.arena_t.total], self.m_dev)
+
+    def train_step(self, images):
+        out = super().train_step(images)
+        if self._packer_t_of is not self._packer:                        # (re)built with the student's, after an eager step
+            self._packer_t, self._packer_t_of = BatchedPacker(self.model_ema, (0,)), self._packer
+        return out
+
+    def state_dict(self, epoch=0):
+        """_TwoViewTrainer's checkpoint plus the teacher (`model_ema`) and the momentum."""
+        sd = super().state_dict(epoch)
+        sd.update(model_ema=self.model_ema.state_dict(), momentum=self.momentum)
+        return sd
+
+    def load_state_dict(self, sd):
+        epoch = super().load_state_dict(sd)
+        self.model_ema.load_state_dict(sd['model_ema'])
+        self.set_schedule(sd.get('momentum'))
         return epoch
 
 

@@ -1,7 +1,9 @@
 """ContrastWrapper / SimSiam / GraphWrapper (reference: lib/modeling/graph_wrappers.py) on the engine, SimCLR (the
 reference's ContrastWrapper trained with the in-batch NT-Xent loss; not in the reference) and SwAV (the same wrapper with
 learned prototypes and the swapped-prediction loss; not in the reference either) and DINO (the same wrapper with prototypes,
-built twice -- student and momentum teacher -- and trained by DINOTrainer; not in the reference either).
+built twice -- student and momentum teacher -- and trained by DINOTrainer; not in the reference either) and MoCoV3 (SimSiam's
+encoder + projector + predictor, built twice -- the teacher without the predictor -- and trained by MoCoV3Trainer; not in the
+reference either).
 
 ``GraphWrapper.forward(x)`` keeps the reference behaviour (MoCo: (b,3,T,H,W) -> (b,FEAT_DIM) unit
 rows; SimSiam and SimCLR: (b,6,T,H,W) -> scalar loss) and is differentiable through torch.autograd as ONE
@@ -277,9 +279,41 @@ class DINO(ContrastWrapper):
         self.prototypes = Prototypes(hid_dim, int(K))
 
 
+class MoCoV3(nn.Module):
+    """Encoder + projector (+ predictor): the student, and built with ``predictor=False`` the momentum teacher, of MoCo v3
+    (Chen, Xie, He 2021).  Modules in this registration order: ``encoder``, ``projection = ProjectionMLP(feature_dim, hid_dim,
+    out_dim)`` and, for the student, ``prediction = PredictionMLP(out_dim, hid_dim, out_dim)`` -- the teacher's parameters are
+    then exactly the leading ones of the student's, which MoCoV3Trainer's one-launch EMA relies on.  The state-dict names are
+    SimSiam's (``encoder.*``, ``projection.*``, ``prediction.*``), so SimSiam checkpoints and every encoder loader read it.
+    ``forward(x)`` / ``fwd``: one view (b,3,T,H,W) -> (b, out_dim) unit rows (predictor outputs for the student, projector outputs
+    for the teacher); the loss (lib.memory.mocov3.MoCoV3Loss, csrc/mocov3.hip) needs both instances and lives in the trainer.
+    Deviation from the paper: the projector's last BatchNorm keeps its affine parameters (ProjectionMLP as it is)."""
+
+    def __init__(self, encoder, out_dim=256, hid_dim=4096, predictor=True):
+        super().__init__()
+        for name, v in (('out_dim', out_dim), ('hid_dim', hid_dim)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 1:
+                raise ValueError('MoCoV3: %s must be a positive integer (got %r)' % (name, v))
+        self.encoder = encoder
+        self.feature_dim = encoder.feature_dim
+        self.projection = ProjectionMLP(self.feature_dim, int(hid_dim), int(out_dim))
+        if predictor:
+            self.prediction = PredictionMLP(int(out_dim), int(hid_dim), int(out_dim))
+        self.has_predictor = bool(predictor)
+
+    def fwd(self, tape, xv):
+        z = self.projection.fwd(tape, self.encoder.fwd(tape, xv))
+        if self.has_predictor:
+            z = self.prediction.fwd(tape, z)
+        return L.f_l2norm(tape, z)
+
+    def forward(self, x):
+        return run_module(self, x)
+
+
 class GraphWrapper(nn.Module):
     def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07, bt_lambda=0.0051,
-                 vic_coeffs=(25.0, 25.0, 1.0), swav_args=(3000, 0.05, 0.1, 3), dino_k=4096):
+                 vic_coeffs=(25.0, 25.0, 1.0), swav_args=(3000, 0.05, 0.1, 3), dino_k=4096, v3_hid=4096, v3_predictor=True):
         super().__init__()
         if mem_type == 'simsiam':
             self.model = SimSiam(encoder=encoder, hid_dim=hid_dim)
@@ -293,6 +327,8 @@ class GraphWrapper(nn.Module):
             self.model = SwAV(encoder, hid_dim, head_type, *swav_args)
         elif mem_type == 'dino':
             self.model = DINO(encoder, hid_dim, head_type, dino_k)
+        elif mem_type == 'mocov3':
+            self.model = MoCoV3(encoder, hid_dim, v3_hid, predictor=v3_predictor)
         else:
             self.model = ContrastWrapper(encoder=encoder, hid_dim=hid_dim, head_type=head_type)
 
