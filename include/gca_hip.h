@@ -743,6 +743,59 @@ int gca_mocov3_bwd(const float* q1, const float* q2, const float* k1, const floa
                    void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * NNCLR: nearest-neighbour contrastive learning (Dwibedi et al. 2021, Algorithm 1) -- the support-set search with its gather,
+ * and the loss gradient to the predictions (csrc/nnclr.hip).  Not in the reference.  The forward loss needs no entry of its
+ * own: gca_mocov3_fwd(q1 = nn1, q2 = nn2, k1 = p1, k2 = p2, w = 1/2) is L(nn1, p2) / 2 + L(nn2, p1) / 2.
+ * Search.  z1, z2 (N, D): the projections of the two views; Q (K, D): the support set (a FIFO of past projections); all
+ * contiguous fp32, unit rows are the caller's business.  Per view v:
+ *   s[v][i,j]  = sum_e z_v[i,e] * Q[j,e]
+ *   key(s)     = s, or -inf where s is NaN
+ *   idx[v][i]  = the smallest j that attains max_j key(s[v][i,j])        (int32, ALWAYS in [0, K), whatever the inputs)
+ *   sim[v][i]  = that key
+ *   nn_v[i,:]  = Q[idx[v][i],:]                                          (copied bit for bit)
+ * idx and sim hold 2 N entries, view 1 first.
+ * Backward.  nn1, nn2, p1, p2 (N, D); row_lse (2 N) as gca_mocov3_fwd(nn1, nn2, p1, p2, ...) wrote it.  Direction 0 has rows nn1
+ * and columns p2, direction 1 rows nn2 and columns p1; per direction, with s[i,j] = (nn[i] . p[j]) * inv_T:
+ *   P[i,j]     = exp(s[i,j] - lse[i])                                    (the softmax runs over the predictions)
+ *   dp[j,:]    = g * w * inv_T / N * ( sum_i P[i,j] nn[i,:] - nn[j,:] ),   g = gscale_host * (gscale_dev ? *gscale_dev : 1)
+ * dp2 comes from direction 0 and dp1 from direction 1.  Nothing flows to nn1 / nn2.
+ * Guarantees:
+ *   products     v_mfma_f32_32x32x2_f32 (exact fp32, fp32 accumulation, one k-ordered fma chain per element); neither a
+ *                (2 N, K) nor an N x N tensor is formed.
+ *   one pass     the search scores a staged tile of Q against the row tiles of BOTH views before the next one is fetched;
+ *                4 row tiles (128 rows of the two views together) sit beside it in LDS, so up to N = 64 per view the support
+ *                set is read once per call, past that once per 128 rows.
+ *   launches     search 2: per-split (best key, best j) pairs to `ws`, then the fold of the splits in split order (the lower
+ *                index wins a tie -- the ONE order on pairs used throughout), idx, sim and the gather.  Backward 2: tiles,
+ *                then the fold of the splits of the streamed rows in split order, the -nn[j,:] term and the scale.
+ *   backward     a workgroup owns a 32-row tile of dp and streams the tiles of nn with their lse; s is recomputed by the
+ *                forward's chain, so N = 1 gives dp exactly 0.  The kernels are gca_mocov3_bwd's (csrc/xview_tile.h) with the
+ *                log-sum-exp taken by streamed row instead of by owned row.
+ *   determinism  no atomics, one owner per output element, fixed fold orders: outputs are bitwise the same from call to call.
+ *   capture      no host sync, allocation or read: both entries can be captured in a hipGraph.
+ *   dispatch     a function of the arguments alone, never of the device.  gca_nnclr_search_path (`aligned`: z1, z2, Q 16-byte
+ *                aligned) and gca_nnclr_bwd_path (`aligned`: every pointer, outputs and ws included) return 1 for the fast path
+ *                (D <= 256, D % 4 == 0, aligned; 4 waves per workgroup, float4 loads with the next piece in flight under the
+ *                current MFMAs), 0 for the generic one (1 wave), and write waves per workgroup and the number of splits.
+ *                Search: kt = ceil(K / 32) tiles, G = ceil(2 ceil(N / 32) / 4) row-tile groups (fast; 2 ceil(N / 32)
+ *                generic), want = clamp(ceil(256 / G), 1, kt), tps = ceil(kt / want), splits = ceil(kt / tps).  Backward:
+ *                gca_mocov3_path's rule.  tests/nnclr_ref.py restates arithmetic and dispatch.
+ * `ws`: gca_nnclr_search_ws_bytes(N, D, K) / gca_nnclr_bwd_ws_bytes(N, D) bytes (always > 0 for valid sizes).
+ * GCA_EINVAL (nothing launched, nothing written; -1 from the ws_bytes functions) for N < 1, N > 65536, D < 1, N * D >= 2^31,
+ * and in the search K < 1, K >= 2^31, K * D >= 2^31, a NULL z1 / z2 / Q / idx / sim / nn1 / nn2 / ws, ws_bytes below
+ * gca_nnclr_search_ws_bytes, nn1 or nn2 overlapping each other, Q, z1 or z2; in the backward entry inv_T or w not finite or
+ * <= 0, a NULL nn1 / nn2 / p1 / p2 / row_lse / dp1 / dp2 / ws, dp1 or dp2 overlapping each other or any of nn1, nn2, p1, p2. */
+int64_t gca_nnclr_search_ws_bytes(int64_t N, int64_t D, int64_t K);
+int gca_nnclr_search_path(int64_t N, int64_t D, int64_t K, int aligned, int32_t* waves, int32_t* splits);
+int gca_nnclr_search(const float* z1, const float* z2, const float* Q, int64_t N, int64_t D, int64_t K, int32_t* idx, float* sim,
+                     float* nn1, float* nn2, void* ws, int64_t ws_bytes, void* stream);
+int64_t gca_nnclr_bwd_ws_bytes(int64_t N, int64_t D);
+int gca_nnclr_bwd_path(int64_t N, int64_t D, int aligned, int32_t* waves, int32_t* splits);
+int gca_nnclr_bwd(const float* nn1, const float* nn2, const float* p1, const float* p2, const float* row_lse, int64_t N,
+                  int64_t D, float inv_T, float w, const float* gscale_dev, float gscale_host, float* dp1, float* dp2, void* ws,
+                  void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

@@ -165,6 +165,12 @@ SIGNATURES = {
     'gca_mocov3_path': (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp]),
     'gca_mocov3_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'gca_mocov3_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    'gca_nnclr_search_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
+    'gca_nnclr_search_path': (c_i32, [c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    'gca_nnclr_search': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'gca_nnclr_bwd_ws_bytes': (c_i64, [c_i64, c_i64]),
+    'gca_nnclr_bwd_path': (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp]),
+    'gca_nnclr_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
     'gca_classifier_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_classifier_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'gca_classifier_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32,

@@ -1273,6 +1273,59 @@ def mocov3_bwd(q1, q2, k1, k2, lse, inv_T, gscale_dev=None, gscale_host=1.0, w=N
     return dq1, dq2
 
 
+# ----------------------------------------------------------------------------- NNCLR
+def nnclr_weight():
+    """The loss weight 1/2 of NNCLR's two directions (exact in fp32)."""
+    return 0.5
+
+
+def nnclr_search(z1, z2, queue):
+    """Nearest support-set row of every row of both views, with the gather (gca_nnclr_search; tests/nnclr_ref.py states the
+    arithmetic): z1, z2 (N, D), queue (K, D) fp32 on the device -> (idx (2, N) int32, sim (2, N) fp32, nn1 (N, D), nn2 (N, D)).
+    idx[v, i] is the smallest j that attains max_j z_v[i] . queue[j] (NaN scores count as -inf; always in [0, K)), sim the
+    score, nn_v[i] = queue[idx[v, i]] bit for bit.  One pass over the queue for both views, no host sync.  ValueError for
+    arguments the kernel entry refuses."""
+    if z1.dim() != 2 or z2.shape != z1.shape or queue.dim() != 2 or queue.shape[1] != z1.shape[1]:
+        raise ValueError('nnclr_search: z1, z2 (N, D) of one shape and queue (K, D) expected (got %s, %s, %s)'
+                         % (tuple(z1.shape), tuple(z2.shape), tuple(queue.shape)))
+    if any(t.dtype is not F32 for t in (z1, z2, queue)):
+        raise ValueError('nnclr_search: fp32 tensors expected (got %s)' % ', '.join(str(t.dtype) for t in (z1, z2, queue)))
+    (N, D), K = z1.shape, queue.shape[0]
+    nbytes = H.lib.gca_nnclr_search_ws_bytes(N, D, K)
+    if nbytes < 0:
+        raise ValueError('nnclr_search: 1 <= N <= 65536, D >= 1, 1 <= K < 2^31, N * D and K * D < 2^31 (got N=%d, D=%d, K=%d)'
+                         % (N, D, K))
+    z1, z2, queue = z1.contiguous(), z2.contiguous(), queue.contiguous()
+    ps = [ptr(t) for t in (z1, z2, queue)]                              # (RuntimeError for host tensors)
+    dev = z1.device
+    idx = torch.empty((2, N), dtype=torch.int32, device=dev)
+    sim = torch.empty((2, N), dtype=F32, device=dev)
+    nn1 = torch.empty((N, D), dtype=F32, device=dev)
+    nn2 = torch.empty((N, D), dtype=F32, device=dev)
+    ws = WS.get(nbytes, dev)
+    H.call('gca_nnclr_search', *ps, N, D, K, ptr(idx), ptr(sim), ptr(nn1), ptr(nn2), ptr(ws), ws.numel(), stream())
+    return idx, sim, nn1, nn2
+
+
+def nnclr_bwd(nn1, nn2, p1, p2, lse, inv_T, gscale_dev=None, gscale_host=1.0, w=None):
+    """d loss / d (p1, p2) of mocov3_fwd(nn1, nn2, p1, p2, inv_T, w=1/2) from its row log-sum-exps (gca_nnclr_bwd: the softmax
+    runs over the predictions, so the gradient goes to the column operand), times gscale_host * (*gscale_dev if given)
+    -> (dp1, dp2).  Nothing flows to nn1, nn2.  w defaults to nnclr_weight()."""
+    N, D, inv_T, w = _mocov3_args(nn1, nn2, p1, p2, inv_T, nnclr_weight() if w is None else w, 'nnclr_bwd')
+    gscale_host = float(gscale_host)
+    if not -3.0e38 < gscale_host < 3.0e38:
+        raise ValueError('nnclr_bwd: gscale_host must be finite in fp32 (got %r)' % gscale_host)
+    if lse.dtype is not F32 or tuple(lse.shape) != (2 * N,):
+        raise ValueError('nnclr_bwd: lse is the (2 N,) fp32 vector of mocov3_fwd (got %s %s)' % (tuple(lse.shape), lse.dtype))
+    nn1, nn2, p1, p2, lse = (t.contiguous() for t in (nn1, nn2, p1, p2, lse))
+    ps = [ptr(t) for t in (nn1, nn2, p1, p2, lse)]
+    dp1 = torch.empty((N, D), dtype=F32, device=p1.device)
+    dp2 = torch.empty((N, D), dtype=F32, device=p1.device)
+    ws = WS.get(H.lib.gca_nnclr_bwd_ws_bytes(N, D), p1.device)
+    H.call('gca_nnclr_bwd', *ps, N, D, inv_T, w, ptr(gscale_dev), gscale_host, ptr(dp1), ptr(dp2), ptr(ws), stream())
+    return dp1, dp2
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

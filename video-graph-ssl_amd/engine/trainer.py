@@ -1,4 +1,4 @@
-"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins, VICReg, SwAV, DINO and MoCo v3) on the HIP engine.
+"""Pre-training step drivers (MoCo, SimSiam, SimCLR, Barlow Twins, VICReg, SwAV, DINO, MoCo v3 and NNCLR) on the HIP engine.
 
 Restates the iteration of tools/train_video_contrast_dis.py:395-454 (_train_moco) and :479-523
 (_train_simsiam) without its host syncs (3x .item() per iteration, :429-431) and defects
@@ -930,6 +930,88 @@ class MoCoV3Trainer(_TwoViewTrainer):
         epoch = super().load_state_dict(sd)
         self.model_ema.load_state_dict(sd['model_ema'])
         self.set_schedule(sd.get('momentum'))
+        return epoch
+
+
+class NNCLRTrainer(_TwoViewTrainer):
+    """NNCLR pre-training (CONTRAST.MEM_TYPE 'nnclr'; output width CROSS.FEAT_DIM, hidden width CONTRAST.NN_HID, support set of
+    CONTRAST.NCE_K rows, temperature CONTRAST.NCE_T): Algorithm 1 of Dwibedi et al. 2021.  The model is
+    lib.modeling.graph_wrappers.NNCLR (encoder + projector + predictor, no momentum encoder); the support set is the `memory`
+    of lib.memory.nnclr.NNCLRLoss.  One step:
+
+        both views through fwd_zp (tape) -> z1, p1, z2, p2     nnclr_search of the PRE-enqueue support set -> nn1, nn2
+        mocov3_fwd(nn1, nn2, p1, p2, w = 1/2)                  nnclr_bwd -> p1, p2 -> tape backward
+        z1 enqueued at the device pointer, pointer advanced    optimizer step
+
+    The queue pointer lives on the device (ptr_dev, as MoCoTrainer's), so replays of the captured step move it; the module's
+    `index` is its host mirror.  `out` carries `loss`, `l12`, `l21` (device scalars), `rank` (2, N) int32 and the neighbours
+    `idx` (2, N) int32 with their scores `sim`.  One GPU only: the support set of the global batch needs an all-gather of the
+    projections between the ranks."""
+
+    def __init__(self, cfg, device, ctx=None, use_graph=True, seed=None):
+        super().__init__(cfg, device, ctx, use_graph, seed)
+        self.contrast = create_contrast(cfg, 0).to(self.device)
+        self.inv_T = 1.0 / self.contrast.T
+        self.K = self.contrast.K
+        self.ptr_dev = torch.zeros(1, dtype=torch.long, device=self.device)
+        self._aux = {}
+
+    def _check_cfg(self, cfg):
+        if cfg.CONTRAST.MEM_TYPE != 'nnclr':
+            raise ValueError('NNCLRTrainer needs CONTRAST.MEM_TYPE == nnclr (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if self.ctx.active:
+            raise NotImplementedError('NNCLRTrainer runs on one GPU: the support set of the global batch needs an all-gather '
+                                      'of the projections between the ranks')
+
+    def _check_model(self, ema):
+        if ema is not None:
+            raise ValueError('NNCLRTrainer needs CONTRAST.MEM_TYPE == nnclr (NNCLR has no momentum encoder)')
+
+    def _loss(self, tape):
+        m = self.model.model
+        x1, x2 = torch.chunk(self._static, 2, dim=1)               # views, read in place through the batch stride
+        z1, p1 = m.fwd_zp(tape, Var(x1))
+        z2, p2 = m.fwd_zp(tape, Var(x2))
+        mem = self.contrast.memory
+        z1t = z1.t.contiguous()
+        idx, sim, nn1, nn2 = ops.nnclr_search(z1t, z2.t.contiguous(), mem)      # the pre-enqueue support set
+        p1t, p2t = p1.t.contiguous(), p2.t.contiguous()
+        loss, lse, rank, _ = ops.mocov3_fwd(nn1, nn2, p1t, p2t, self.inv_T, w=ops.nnclr_weight(), want_rank=True)
+        ops.queue_enqueue(mem, z1t, 0, ptr_dev=self.ptr_dev)
+        ops.queue_advance(self.ptr_dev, z1t.shape[0], self.K)
+        self._aux = dict(l12=loss[1:2], l21=loss[2:3], rank=rank, idx=idx, sim=sim)
+        lv = Var(loss[:1], True)
+
+        def back():
+            # the fp16-storage loss scale folds into the products' scale
+            dp1, dp2 = ops.nnclr_bwd(nn1, nn2, p1t, p2t, lse, self.inv_T, gscale_dev=ops.LOSS_SCALE_STATE[0])
+            p1.add_grad(dp1)
+            p2.add_grad(dp2)
+        tape.record(back)
+        return lv
+
+    def _outputs(self, lv):
+        return dict(loss=lv.t, **self._aux)
+
+    def train_step(self, images):
+        b = (images.stage.out_shape() if isinstance(images, StagedBatch) else images.shape)[0]
+        if b > self.K:
+            raise ValueError('NNCLRTrainer: cannot enqueue %d rows into a support set of %d' % (b, self.K))
+        out = super().train_step(images)
+        self.contrast.index = (self.contrast.index + b) % self.K          # host mirror of ptr_dev
+        return out
+
+    def state_dict(self, epoch=0):
+        """_TwoViewTrainer's checkpoint plus the support set (`contrast`) and its pointer (`queue_index`)."""
+        sd = super().state_dict(epoch)
+        sd.update(contrast=self.contrast.state_dict(), queue_index=int(self.contrast.index))
+        return sd
+
+    def load_state_dict(self, sd):
+        epoch = super().load_state_dict(sd)
+        self.contrast.load_state_dict(sd['contrast'])
+        self.contrast.index = int(sd.get('queue_index', 0)) % self.K
+        self.ptr_dev.fill_(self.contrast.index)
         return epoch
 
 

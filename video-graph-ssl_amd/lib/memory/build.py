@@ -3,13 +3,14 @@ HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no 
 'barlow' (Barlow Twins' cross-correlation loss, likewise the loss module itself) / 'vicreg' (the variance / invariance /
 covariance loss, likewise) / 'swav' (the swapped-prediction loss, likewise; the prototypes live in the model) / 'dino' (the centred-teacher
 self-distillation loss; its centre is the module's one buffer) / 'mocov3' (MoCo v3's symmetrised cross-view InfoNCE at
-CONTRAST.NCE_T: no queue, the loss module itself; the momentum teacher is the second model of create_visual_model), CRITERION
-'crossentropy'."""
+CONTRAST.NCE_T: no queue, the loss module itself; the momentum teacher is the second model of create_visual_model) / 'nnclr' (nearest-neighbour contrast against a support set:
+a FIFO of CONTRAST.NCE_K projections of width CROSS.FEAT_DIM, temperature CONTRAST.NCE_T), CRITERION 'crossentropy'."""
 from .barlow import BarlowTwinsLoss
 from .criterion import NCESoftmaxLoss
 from .dino import DINOLoss
 from .mem_moco import RGBMoCo
 from .mocov3 import MoCoV3Loss
+from .nnclr import NNCLRLoss
 from .ntxent import NTXent
 from .swav import SwAVLoss
 from .vicreg import VICRegLoss
@@ -34,6 +35,8 @@ def create_contrast(cfg, n_data):
         return DINOLoss(cfg.CONTRAST.DINO_K, cfg.CONTRAST.DINO_TS, cfg.CONTRAST.DINO_TT, cfg.CONTRAST.DINO_CM)
     if cfg.CONTRAST.MEM_TYPE == 'mocov3':
         return MoCoV3Loss(cfg.CONTRAST.NCE_T)
+    if cfg.CONTRAST.MEM_TYPE == 'nnclr':
+        return NNCLRLoss(cfg.CROSS.FEAT_DIM, cfg.CONTRAST.NCE_K, cfg.CONTRAST.NCE_T)
     raise NotImplementedError('mem not suported: {}'.format(cfg.CONTRAST.MEM_TYPE))
 
 

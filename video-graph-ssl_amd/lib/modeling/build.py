@@ -23,7 +23,8 @@ def create_video_model(cfg):
 def create_visual_model(cfg):
     """-> (model, model_ema | None); MoCo has a key encoder and DINO a momentum teacher, a second wrapper of the same layout
     (prototypes included); MoCo v3 ('mocov3': out = CROSS.FEAT_DIM, hidden width CONTRAST.V3_HID) has a momentum teacher without
-    the predictor; every other MEM_TYPE returns None.  NOTE: the
+    the predictor; NNCLR ('nnclr': out = CROSS.FEAT_DIM, hidden width CONTRAST.NN_HID) has no second model; every other
+    MEM_TYPE returns None.  NOTE: the
     reference never forwards MODEL.AUG_FLAG (dead code); here the flag is honoured so the graph block can actually be
     switched on."""
     model = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE,
@@ -32,7 +33,8 @@ def create_visual_model(cfg):
                                           for k, d in (('VIC_SIM', 25.0), ('VIC_STD', 25.0), ('VIC_COV', 1.0))),
                          swav_args=tuple(getattr(cfg.CONTRAST, k, d)
                                          for k, d in (('SWAV_K', 3000), ('SWAV_EPS', 0.05), ('SWAV_T', 0.1), ('SWAV_ITERS', 3))),
-                         dino_k=getattr(cfg.CONTRAST, 'DINO_K', 4096), v3_hid=getattr(cfg.CONTRAST, 'V3_HID', 4096))
+                         dino_k=getattr(cfg.CONTRAST, 'DINO_K', 4096), v3_hid=getattr(cfg.CONTRAST, 'V3_HID', 4096),
+                         nn_hid=getattr(cfg.CONTRAST, 'NN_HID', 2048))
     model_ema = None
     if cfg.CONTRAST.MEM_TYPE == 'moco':
         model_ema = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE)

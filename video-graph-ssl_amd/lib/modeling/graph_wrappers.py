@@ -3,7 +3,8 @@ reference's ContrastWrapper trained with the in-batch NT-Xent loss; not in the r
 learned prototypes and the swapped-prediction loss; not in the reference either) and DINO (the same wrapper with prototypes,
 built twice -- student and momentum teacher -- and trained by DINOTrainer; not in the reference either) and MoCoV3 (SimSiam's
 encoder + projector + predictor, built twice -- the teacher without the predictor -- and trained by MoCoV3Trainer; not in the
-reference either).
+reference either) and NNCLR (the same three modules once, returning projection AND prediction, trained by NNCLRTrainer; not
+in the reference either).
 
 ``GraphWrapper.forward(x)`` keeps the reference behaviour (MoCo: (b,3,T,H,W) -> (b,FEAT_DIM) unit
 rows; SimSiam and SimCLR: (b,6,T,H,W) -> scalar loss) and is differentiable through torch.autograd as ONE
@@ -14,7 +15,7 @@ import torch.nn as nn
 from .project_head import BarlowProjector, PredictionMLP, ProjectHead, ProjectionMLP
 from ...engine import layers as L, ops
 from ...engine.autograd_bridge import run_module
-from ...engine.tape import Var
+from ...engine.tape import Tape, Var
 from ..memory.vicreg import check_coeffs
 
 
@@ -311,9 +312,42 @@ class MoCoV3(nn.Module):
         return run_module(self, x)
 
 
+class NNCLR(nn.Module):
+    """Encoder + projector + predictor of NNCLR (Dwibedi et al. 2021).  Modules in MoCoV3's registration order: ``encoder``,
+    ``projection = ProjectionMLP(feature_dim, hid_dim, out_dim)``, ``prediction = PredictionMLP(out_dim, hid_dim, out_dim)``;
+    the state-dict names are SimSiam's (``encoder.*``, ``projection.*``, ``prediction.*``), so SimSiam checkpoints and every
+    encoder loader read it.  ``fwd_zp(tape, xv)``: one view (b,3,T,H,W) -> (z, p), the projection (what the support set holds and
+    the search uses) and the prediction, both (b, out_dim) unit rows; ``fwd`` / ``forward(x)`` give p.  The loss
+    (lib.memory.nnclr.NNCLRLoss, csrc/nnclr.hip) owns the support set and lives in the trainer.  Deviations from the paper: the
+    predictor shares the projector's hidden width, and the projector's last BatchNorm keeps its affine parameters."""
+
+    def __init__(self, encoder, out_dim=256, hid_dim=2048):
+        super().__init__()
+        for name, v in (('out_dim', out_dim), ('hid_dim', hid_dim)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 1:
+                raise ValueError('NNCLR: %s must be a positive integer (got %r)' % (name, v))
+        self.encoder = encoder
+        self.feature_dim = encoder.feature_dim
+        self.projection = ProjectionMLP(self.feature_dim, int(hid_dim), int(out_dim))
+        self.prediction = PredictionMLP(int(out_dim), int(hid_dim), int(out_dim))
+
+    def fwd_zp(self, tape, xv):
+        z = self.projection.fwd(tape, self.encoder.fwd(tape, xv))
+        p = self.prediction.fwd(tape, z)
+        # z is used detached (the arg-max of the search has no gradient): its normalisation stays off the tape
+        return L.f_l2norm(Tape(False), z), L.f_l2norm(tape, p)
+
+    def fwd(self, tape, xv):
+        return self.fwd_zp(tape, xv)[1]
+
+    def forward(self, x):
+        return run_module(self, x)
+
+
 class GraphWrapper(nn.Module):
     def __init__(self, encoder, hid_dim=1024, head_type='mlp', mem_type='simsiam', nce_t=0.07, bt_lambda=0.0051,
-                 vic_coeffs=(25.0, 25.0, 1.0), swav_args=(3000, 0.05, 0.1, 3), dino_k=4096, v3_hid=4096, v3_predictor=True):
+                 vic_coeffs=(25.0, 25.0, 1.0), swav_args=(3000, 0.05, 0.1, 3), dino_k=4096, v3_hid=4096, v3_predictor=True,
+                 nn_hid=2048):
         super().__init__()
         if mem_type == 'simsiam':
             self.model = SimSiam(encoder=encoder, hid_dim=hid_dim)
@@ -329,6 +363,8 @@ class GraphWrapper(nn.Module):
             self.model = DINO(encoder, hid_dim, head_type, dino_k)
         elif mem_type == 'mocov3':
             self.model = MoCoV3(encoder, hid_dim, v3_hid, predictor=v3_predictor)
+        elif mem_type == 'nnclr':
+            self.model = NNCLR(encoder, hid_dim, nn_hid)
         else:
             self.model = ContrastWrapper(encoder=encoder, hid_dim=hid_dim, head_type=head_type)
 
