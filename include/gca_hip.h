@@ -796,6 +796,42 @@ int gca_nnclr_bwd(const float* nn1, const float* nn2, const float* p1, const flo
                   void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * ReSSL: relational self-supervised learning (Zheng et al. 2021) -- the teacher-weighted relational loss of student rows
+ * against the MoCo queue, and its gradient to the student (csrc/ressl.hip).  Not in the reference.
+ * q, k (N, D): student and teacher rows (nothing flows to k); Q (K, D): the queue BEFORE this step's enqueue; all contiguous fp32.
+ *   s[i,j] = inv_Ts q_i . Q_j,  t[i,j] = inv_Tt k_i . Q_j      exact-fp32 matrix cores, one k-ordered chain per score
+ *   row_lse[i] = logsumexp_j s[i,:],  row_lse[N + i] = logsumexp_j t[i,:];   Ps = exp(s - lse_s),  Pt = exp(t - lse_t)
+ *   row_loss[i] = lse_s[i] - sum_j Pt[i,j] s[i,j];   out[0] = mean_i row_loss[i]
+ *   out[1] = mean_i (lse_t[i] - sum_j Pt[i,j] t[i,j])             the teacher's entropy
+ *   dq[i,:] = g inv_Ts / N (sum_j Ps[i,j] Q_j - sum_j Pt[i,j] Q_j),  g = gscale_host * (*gscale_dev if not NULL)
+ *   forward      ONE pass over Q: six running scalars per row (two maxima, two sums, two teacher-weighted sums), one record
+ *                per (K-split, row) in `ws`, folded in split order by a second, one-workgroup launch that also takes the two
+ *                means through one fixed tree.  Columns past K are -inf before the maximum.  No (N, K) tensor.
+ *   backward     grid (K-splits, row tiles, 2 sides): side 0 owns q with lse_s and inv_Ts, side 1 owns k with lse_t and inv_Tt,
+ *                the same instructions; P is recomputed by the forward's chain and multiplied into the streamed rows from
+ *                registers; one slab per (split, side) in `ws`, summed in split order by the launch that writes dq.
+ *   determinism  no atomics, one owner per output element, fixed fold orders: outputs are bitwise the same from call to call.
+ *   capture      no host sync, allocation or read: both entries can be captured in a hipGraph.
+ *   dispatch     a function of the arguments alone.  gca_ressl_fwd_path (`aligned`: q, k, Q 16-byte aligned) and
+ *                gca_ressl_bwd_path (`aligned`: q, k, Q and ws) return 1 for the fast path (D <= 256, D % 4 == 0, aligned;
+ *                4 waves), 0 for the generic one (1 wave), and write waves per workgroup and the number of splits:
+ *                kt = ceil(K / 32), G = ceil(N / 32) (forward) or 2 ceil(N / 32) (backward), want = clamp(ceil(256 / G), 1,
+ *                ceil(kt / waves)), tps = ceil(kt / want), splits = ceil(kt / tps) -- no split is empty.
+ * `ws`: gca_ressl_fwd_ws_bytes / gca_ressl_bwd_ws_bytes (N, D, K) bytes (always > 0 for valid sizes).
+ * GCA_EINVAL (nothing launched, nothing written; -1 from the ws_bytes functions) for N < 1, N > 65536, D < 1, K < 1, K >= 2^31,
+ * N * D or K * D >= 2^31, inv_Ts or inv_Tt not finite or <= 0, a NULL pointer other than gscale_dev, ws_bytes too small, an
+ * output (row_lse, row_loss, out; dq) overlapping an input or another output. */
+int64_t gca_ressl_fwd_ws_bytes(int64_t N, int64_t D, int64_t K);
+int64_t gca_ressl_bwd_ws_bytes(int64_t N, int64_t D, int64_t K);
+int gca_ressl_fwd_path(int64_t N, int64_t D, int64_t K, int aligned, int32_t* waves, int32_t* splits);
+int gca_ressl_bwd_path(int64_t N, int64_t D, int64_t K, int aligned, int32_t* waves, int32_t* splits);
+int gca_ressl_fwd(const float* q, const float* k, const float* Q, int64_t N, int64_t D, int64_t K, float inv_Ts, float inv_Tt,
+                  float* row_lse, float* row_loss, float* out, void* ws, int64_t ws_bytes, void* stream);
+int gca_ressl_bwd(const float* q, const float* k, const float* Q, const float* row_lse, int64_t N, int64_t D, int64_t K,
+                  float inv_Ts, float inv_Tt, const float* gscale_dev, float gscale_host, float* dq, void* ws, int64_t ws_bytes,
+                  void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Action-recognition class head (lib/modeling/model_wrappers.py:74-82,99-117: nn.Linear on the pooled features) fused with
  * nn.CrossEntropyLoss (tools/train_ds.py:111-112) and accuracy() (:120).  x (b, F), w (C, F), logits (b, C) contiguous fp32;
  * bias (C) or NULL; target (b) int64.

@@ -171,6 +171,12 @@ SIGNATURES = {
     'gca_nnclr_bwd_ws_bytes': (c_i64, [c_i64, c_i64]),
     'gca_nnclr_bwd_path': (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp]),
     'gca_nnclr_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    'gca_ressl_fwd_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
+    'gca_ressl_bwd_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
+    'gca_ressl_fwd_path': (c_i32, [c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    'gca_ressl_bwd_path': (c_i32, [c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    'gca_ressl_fwd': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'gca_ressl_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp]),
     'gca_classifier_ws_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'gca_classifier_fwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'gca_classifier_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32,

@@ -1326,6 +1326,60 @@ def nnclr_bwd(nn1, nn2, p1, p2, lse, inv_T, gscale_dev=None, gscale_host=1.0, w=
     return dp1, dp2
 
 
+# ----------------------------------------------------------------------------- ReSSL
+def _ressl_args(q, k, queue, inv_Ts, inv_Tt, what):
+    """Host-side refusals of gca_ressl_fwd / _bwd (before any device is touched) -> (N, D, K, inv_Ts, inv_Tt)."""
+    if q.dim() != 2 or k.shape != q.shape or queue.dim() != 2 or queue.shape[1] != q.shape[1]:
+        raise ValueError('%s: q, k (N, D) of one shape and queue (K, D) expected (got %s, %s, %s)'
+                         % (what, tuple(q.shape), tuple(k.shape), tuple(queue.shape)))
+    if any(t.dtype is not F32 for t in (q, k, queue)):
+        raise ValueError('%s: fp32 tensors expected (got %s)' % (what, ', '.join(str(t.dtype) for t in (q, k, queue))))
+    (N, D), K = q.shape, queue.shape[0]
+    if N < 1 or N > 65536 or D < 1 or K < 1 or K >= 2 ** 31 or N * D >= 2 ** 31 or K * D >= 2 ** 31:
+        raise ValueError('%s: 1 <= N <= 65536, D >= 1, 1 <= K < 2^31, N * D and K * D < 2^31 (got N=%d, D=%d, K=%d)'
+                         % (what, N, D, K))
+    inv_Ts, inv_Tt = float(inv_Ts), float(inv_Tt)
+    for name, v in (('1 / Ts', inv_Ts), ('1 / Tt', inv_Tt)):
+        if not 0.0 < v < 3.0e38:
+            raise ValueError('%s: %s must be positive and finite in fp32 (got %r)' % (what, name, v))
+    return N, D, K, inv_Ts, inv_Tt
+
+
+def ressl_fwd(q, k, queue, inv_Ts, inv_Tt):
+    """ReSSL's relational loss (gca_ressl_fwd; tests/ressl_ref.py states the arithmetic): student rows q and teacher rows k,
+    (N, D) fp32, against the (K, D) queue -> (loss (2,): mean_i loss_i and the teacher's mean entropy; row_lse (2 N,): the
+    log-sum-exps of q Q^T / Ts, then of k Q^T / Tt; row_loss (N,)), all on the device.  loss_i = -sum_j softmax(t_i)_j
+    log softmax(s_i)_j.  One pass over the queue, nothing of size K written.  ValueError for arguments the kernel entry refuses."""
+    N, D, K, inv_Ts, inv_Tt = _ressl_args(q, k, queue, inv_Ts, inv_Tt, 'ressl_fwd')
+    q, k, queue = q.contiguous(), k.contiguous(), queue.contiguous()
+    ps = [ptr(t) for t in (q, k, queue)]                                # (RuntimeError for host tensors)
+    dev = q.device
+    loss = torch.empty(2, dtype=F32, device=dev)
+    row_lse = torch.empty(2 * N, dtype=F32, device=dev)
+    row_loss = torch.empty(N, dtype=F32, device=dev)
+    ws = WS.get(H.lib.gca_ressl_fwd_ws_bytes(N, D, K), dev)
+    H.call('gca_ressl_fwd', *ps, N, D, K, inv_Ts, inv_Tt, ptr(row_lse), ptr(row_loss), ptr(loss), ptr(ws), ws.numel(), stream())
+    return loss, row_lse, row_loss
+
+
+def ressl_bwd(q, k, queue, row_lse, inv_Ts, inv_Tt, gscale_dev=None, gscale_host=1.0):
+    """d loss / d q of ressl_fwd from its row log-sum-exps, times gscale_host * (*gscale_dev if given) -> dq (N, D):
+    g / (N Ts) (softmax(s) - softmax(t)) Q.  `queue` must still be the queue ressl_fwd saw.  Nothing flows to k."""
+    N, D, K, inv_Ts, inv_Tt = _ressl_args(q, k, queue, inv_Ts, inv_Tt, 'ressl_bwd')
+    gscale_host = float(gscale_host)
+    if not -3.0e38 < gscale_host < 3.0e38:
+        raise ValueError('ressl_bwd: gscale_host must be finite in fp32 (got %r)' % gscale_host)
+    if row_lse.dtype is not F32 or tuple(row_lse.shape) != (2 * N,):
+        raise ValueError('ressl_bwd: row_lse is the (2 N,) fp32 vector of ressl_fwd (got %s %s)'
+                         % (tuple(row_lse.shape), row_lse.dtype))
+    q, k, queue, row_lse = q.contiguous(), k.contiguous(), queue.contiguous(), row_lse.contiguous()
+    ps = [ptr(t) for t in (q, k, queue, row_lse)]
+    dq = torch.empty((N, D), dtype=F32, device=q.device)
+    ws = WS.get(H.lib.gca_ressl_bwd_ws_bytes(N, D, K), q.device)
+    H.call('gca_ressl_bwd', *ps, N, D, K, inv_Ts, inv_Tt, ptr(gscale_dev), gscale_host, ptr(dq), ptr(ws), ws.numel(), stream())
+    return dq
+
+
 # ----------------------------------------------------------------------------- class head
 def _classifier_args(x, w, bias, target, what):
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:

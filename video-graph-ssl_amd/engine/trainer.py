@@ -460,6 +460,43 @@ class MoCoTrainer(_TrainerBase):
         return int(sd.get('epoch', 0))
 
 
+class ReSSLTrainer(MoCoTrainer):
+    """ReSSL pre-training (CONTRAST.MEM_TYPE 'ressl'; queue of CONTRAST.NCE_K rows of width CROSS.FEAT_DIM, student / teacher
+    temperatures CONTRAST.RESSL_TS / RESSL_TT, teacher momentum CONTRAST.ALPHA): MoCoTrainer's step with the relational loss in
+    InfoNCE's place.  The model and its momentum teacher are MoCo's, the queue is the `memory` of lib.memory.ressl.ReSSLLoss.
+    After both encoder forwards:
+
+        ressl_fwd(q, k, PRE-enqueue queue)      ressl_bwd -> q.grad (x loss scale / world)
+        all_k enqueued at the device pointer, pointer advanced      tape backward
+
+    The gradient is taken before the enqueue, so no overwritten rows are saved.  Key encoder on the second stream, packers,
+    graph capture, the EMA, checkpoints and the StagedBatch input are inherited.  `out` carries `loss` and `ent` (the teacher's
+    mean entropy over the queue: the collapse monitor), `row_loss` (b,) and the query features `q`.  One GPU only: the
+    inherited multi-GPU path is untested with this loss."""
+
+    def __init__(self, cfg, device, ctx=None, use_graph=True, seed=None):
+        if cfg.CONTRAST.MEM_TYPE != 'ressl':
+            raise ValueError('ReSSLTrainer needs CONTRAST.MEM_TYPE == ressl (got %r)' % (cfg.CONTRAST.MEM_TYPE,))
+        if ctx is not None and ctx.active:
+            raise NotImplementedError('ReSSLTrainer runs on one GPU: the inherited multi-GPU step is untested with this loss')
+        super().__init__(cfg, device, ctx, use_graph, seed)
+        self.inv_Ts, self.inv_Tt = 1.0 / self.contrast.Ts, 1.0 / self.contrast.Tt
+
+    def _phase_query_rest(self, tape, qv, upto=0):
+        s = self._static
+        mem = self.contrast.memory
+        loss, row_lse, row_loss = ops.ressl_fwd(qv.t, s['k'], mem, self.inv_Ts, self.inv_Tt)
+        qv.grad = ops.ressl_bwd(qv.t, s['k'], mem, row_lse, self.inv_Ts, self.inv_Tt, gscale_dev=self.scale_state,
+                                gscale_host=1.0 / self.ctx.world)
+        ops.queue_enqueue(mem, s['all_k'], 0, ptr_dev=self.ptr_dev)
+        ops.queue_advance(self.ptr_dev, s['all_k'].shape[0], self.K)
+        self.out = dict(loss=loss[:1], ent=loss[1:], row_loss=row_loss, q=qv.t)
+        self._backward(tape, upto)
+        self._tape = tape if upto > 0 else None
+        if upto == 0:
+            self._unpack('q')
+
+
 class _TwoViewTrainer(_TrainerBase):
     """One encoder, both views of a (b, 6, T, H, W) batch through it with gradients, a loss formed inside the model
     (``model.fwd`` returns the loss Var): the step that SimSiamTrainer and SimCLRTrainer share.  A subclass checks its

@@ -89,7 +89,8 @@ def get_defaults():
         'CONTRAST': dict(MEM_TYPE='bank', NCE_K=65536, NCE_T=0.07, NCE_M=0.5, ALPHA=0.999, JIGSAW=False,
                          BT_LAMBDA=0.0051, VIC_SIM=25.0, VIC_STD=25.0, VIC_COV=1.0,
                          SWAV_K=3000, SWAV_EPS=0.05, SWAV_T=0.1, SWAV_ITERS=3,
-                         DINO_K=4096, DINO_TS=0.1, DINO_TT=0.04, DINO_CM=0.9, V3_HID=4096, NN_HID=2048),
+                         DINO_K=4096, DINO_TS=0.1, DINO_TT=0.04, DINO_CM=0.9, V3_HID=4096, NN_HID=2048,
+                         RESSL_TS=0.1, RESSL_TT=0.04),
         'CROSS': dict(FEAT_DIM=128, HEAD_TYPE='mlp', MEM=None, BETA=0.5, MODALITY='visual',
                       CRITERION='crossentropy'),
     })

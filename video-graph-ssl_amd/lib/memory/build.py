@@ -4,7 +4,9 @@ HIP path: MEM_TYPE 'moco' (visual) / 'simsiam' / 'simclr' (in-batch NT-Xent: no 
 covariance loss, likewise) / 'swav' (the swapped-prediction loss, likewise; the prototypes live in the model) / 'dino' (the centred-teacher
 self-distillation loss; its centre is the module's one buffer) / 'mocov3' (MoCo v3's symmetrised cross-view InfoNCE at
 CONTRAST.NCE_T: no queue, the loss module itself; the momentum teacher is the second model of create_visual_model) / 'nnclr' (nearest-neighbour contrast against a support set:
-a FIFO of CONTRAST.NCE_K projections of width CROSS.FEAT_DIM, temperature CONTRAST.NCE_T), CRITERION 'crossentropy'."""
+a FIFO of CONTRAST.NCE_K projections of width CROSS.FEAT_DIM, temperature CONTRAST.NCE_T) / 'ressl' (the relational loss over
+the MoCo queue: CONTRAST.NCE_K anchors of width CROSS.FEAT_DIM, student / teacher temperatures CONTRAST.RESSL_TS / RESSL_TT; the
+momentum teacher is the second model of create_visual_model), CRITERION 'crossentropy'."""
 from .barlow import BarlowTwinsLoss
 from .criterion import NCESoftmaxLoss
 from .dino import DINOLoss
@@ -12,6 +14,7 @@ from .mem_moco import RGBMoCo
 from .mocov3 import MoCoV3Loss
 from .nnclr import NNCLRLoss
 from .ntxent import NTXent
+from .ressl import ReSSLLoss
 from .swav import SwAVLoss
 from .vicreg import VICRegLoss
 
@@ -37,6 +40,8 @@ def create_contrast(cfg, n_data):
         return MoCoV3Loss(cfg.CONTRAST.NCE_T)
     if cfg.CONTRAST.MEM_TYPE == 'nnclr':
         return NNCLRLoss(cfg.CROSS.FEAT_DIM, cfg.CONTRAST.NCE_K, cfg.CONTRAST.NCE_T)
+    if cfg.CONTRAST.MEM_TYPE == 'ressl':
+        return ReSSLLoss(cfg.CROSS.FEAT_DIM, cfg.CONTRAST.NCE_K, cfg.CONTRAST.RESSL_TS, cfg.CONTRAST.RESSL_TT)
     raise NotImplementedError('mem not suported: {}'.format(cfg.CONTRAST.MEM_TYPE))
 
 

@@ -23,8 +23,8 @@ def create_video_model(cfg):
 def create_visual_model(cfg):
     """-> (model, model_ema | None); MoCo has a key encoder and DINO a momentum teacher, a second wrapper of the same layout
     (prototypes included); MoCo v3 ('mocov3': out = CROSS.FEAT_DIM, hidden width CONTRAST.V3_HID) has a momentum teacher without
-    the predictor; NNCLR ('nnclr': out = CROSS.FEAT_DIM, hidden width CONTRAST.NN_HID) has no second model; every other
-    MEM_TYPE returns None.  NOTE: the
+    the predictor; NNCLR ('nnclr': out = CROSS.FEAT_DIM, hidden width CONTRAST.NN_HID) has no second model; ReSSL ('ressl') has MoCo's model and MoCo's key encoder as
+    its momentum teacher; every other MEM_TYPE returns None.  NOTE: the
     reference never forwards MODEL.AUG_FLAG (dead code); here the flag is honoured so the graph block can actually be
     switched on."""
     model = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE,
@@ -36,7 +36,7 @@ def create_visual_model(cfg):
                          dino_k=getattr(cfg.CONTRAST, 'DINO_K', 4096), v3_hid=getattr(cfg.CONTRAST, 'V3_HID', 4096),
                          nn_hid=getattr(cfg.CONTRAST, 'NN_HID', 2048))
     model_ema = None
-    if cfg.CONTRAST.MEM_TYPE == 'moco':
+    if cfg.CONTRAST.MEM_TYPE in ('moco', 'ressl'):
         model_ema = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE)
     elif cfg.CONTRAST.MEM_TYPE == 'dino':
         model_ema = GraphWrapper(_encoder(cfg), cfg.CROSS.FEAT_DIM, cfg.CROSS.HEAD_TYPE, cfg.CONTRAST.MEM_TYPE,
