@@ -14,6 +14,8 @@ layer's number, whatever the model-level statistic does.
               forward and backward, against the oracle block in fp64.
   configs[0]  the YAML's own workload: b = 2, K = 256, S3D at 16 frames and R(2+1)D-18 at 8 frames, 112 x 112 --
               full MoCo iterations from configs/visual_moco.yaml's keys against oracle.moco.moco_train_step.
+
+The tuned launch codes of configs[3] / configs[4] and of configs[1] in bf16x3 are held per layer by tests/test_gpu_tuned.py.
 """
 import os
 
