@@ -61,8 +61,10 @@ typedef struct {
   int32_t kd, kh, kw;          /* kernel                        */
   int32_t sd, sh, sw;          /* stride                        */
   int32_t pd, ph, pw;          /* zero padding                  */
-  int32_t OD, OH, OW;          /* output spatial (caller-computed, checked).  Each tensor must hold
-                                  < 2^30 elements (32-bit byte offsets inside the kernels). */
+  int32_t OD, OH, OW;          /* output spatial (caller-computed, checked).  Each activation tensor must span
+                                  at most 0xfffff000 bytes (32-bit byte offsets through buffer resources inside
+                                  the kernels): <= 2^30 - 1024 fp32 elements, < 2^30 fp16 elements.  A larger
+                                  one is refused (GCA_EINVAL). */
   int64_t x_batch_stride;      /* elements between consecutive clips of x; 0 = C*D*H*W (contiguous).
                                   Lets the two views of a (b,6,T,H,W) batch be read in place
                                   (tools/train_video_contrast_dis.py:404 torch.chunk on dim 1).

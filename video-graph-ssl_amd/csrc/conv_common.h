@@ -80,6 +80,11 @@ __device__ __forceinline__ float half_wave_sum_hi(float v) {
   return v;
 }
 
+// Byte ranges of buffer resources are 32-bit: a range past BUF_MAX_BYTES is clamped to it, or refused where the whole range
+// must be addressable -- geom_ok refuses an activation tensor larger than this, so for x, y, dy and dx the clamp never cuts.
+constexpr long long BUF_MAX_BYTES = 0xfffff000LL;
+inline unsigned clamp_buf_bytes(long long b) { return b > BUF_MAX_BYTES ? (unsigned)BUF_MAX_BYTES : (unsigned)b; }
+
 inline bool geom_ok(const gca_conv_geom* g) {
   if (!g) return false;
   if (g->N <= 0 || g->C <= 0 || g->D <= 0 || g->H <= 0 || g->W <= 0 || g->K <= 0) return false;
@@ -90,12 +95,16 @@ inline bool geom_ok(const gca_conv_geom* g) {
   const int oh = (g->H + 2 * g->ph - g->kh) / g->sh + 1;
   const int ow = (g->W + 2 * g->pw - g->kw) / g->sw + 1;
   if (od != g->OD || oh != g->OH || ow != g->OW || od <= 0 || oh <= 0 || ow <= 0) return false;
-  // the kernels address both tensors with 32-bit byte offsets from their base: < 2^30 elements (4 GiB) each
+  // the kernels address both tensors with 32-bit byte offsets from their base, through buffer resources whose byte range
+  // ends at BUF_MAX_BYTES at the latest: < 2^30 elements each, and no more than BUF_MAX_BYTES bytes (2^30 - 1024 fp32
+  // elements) -- a larger tensor would read its tail as zeros and drop the stores to it
   const long long cdhw = (long long)g->C * g->D * g->H * g->W;
   if (g->x_batch_stride != 0 && g->x_batch_stride < cdhw) return false;
   const long long in_elems = (long long)g->N * (g->x_batch_stride ? g->x_batch_stride : cdhw);
   const long long out_elems = (long long)g->N * g->K * od * oh * ow;
   if (in_elems >= (1LL << 30) || out_elems >= (1LL << 30)) return false;
+  const long long es = g->act_f16 == 1 ? 2 : 4;
+  if (in_elems * es > BUF_MAX_BYTES || out_elems * es > BUF_MAX_BYTES) return false;
   for (int v : {g->tune_fwd_bm, g->tune_dgrad_bm}) if (v != 0 && !((v & 1023) % 32 == 0 && (v & 1023) >= 32 && (v & 1023) <= 160 && ((v >> 10) <= 2 || (v >> 10) == 4 || (v >> 10) == 8))) return false;   // | 1024 float4 gathers, | 2048 LDS halo, | 4096 stem, | 8192 pointwise fp16 GEMM
   for (int v : {g->tune_fwd_box, g->tune_dgrad_box}) if (v < 0 || v > 0xffffff) return false;
   if (g->act_f16 != 0 && g->act_f16 != 1) return false;
@@ -107,11 +116,6 @@ inline bool geom_ok(const gca_conv_geom* g) {
 }
 
 inline int taps(const gca_conv_geom* g) { return g->kd * g->kh * g->kw; }
-
-// Byte ranges of buffer resources are 32-bit: a range past BUF_MAX_BYTES is clamped to it (the kernels address < 2^30
-// elements of 4 bytes from the base, geom_ok), or refused where the whole range must be addressable.
-constexpr long long BUF_MAX_BYTES = 0xfffff000LL;
-inline unsigned clamp_buf_bytes(long long b) { return b > BUF_MAX_BYTES ? (unsigned)BUF_MAX_BYTES : (unsigned)b; }
 
 // ---- weight gradient (conv3d_wgrad*.hip) --------------------------------------------------------------------------------
 // Parameter blocks of the weight-gradient kernels.  Each kernel file takes its block by a derived type of its own
